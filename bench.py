@@ -16,7 +16,15 @@ With N > 1 the same run ALSO times the strong-scaling mode (`"strong"` in the JS
 primary line): ONE frame per step cut into 2,048-ray tiles dealt round-robin over the ranks (nerfart_amd.dist.render_sharded,
 how a single 960 x 540 frame of cfg 5 is sharded) + one all_gather, value = rays of that one frame / max-over-ranks time.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (fused encode + SDF MLP, k_sdf_only): achieved =
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`) with the run's configuration; `roofline`, `cpu_baseline` and `secondary` are null and the
+per-kernel / algorithmic-work fields of `config` too.  --full adds everything below: the timed steps are profiled (the library's per-launch
+events), and the secondaries, the CPU baseline and its parity checks run after them (--no-secondary / --no-cpu-baseline leave parts out).
+--dump-outputs DIR writes what the last timed step returned to its caller (render_fn's extras dict, rgb and depth among its arrays; at
+N > 1 also the all-gathered tiles, or with --shard tiles the assembled frame of dist.render_sharded) as DIR/<name>.npy in float32 (float64 for integer arrays) - rank 0's, at most 64 MB in all - so that two builds can be
+compared output for output: the inputs (seeded scene, camera orbit) are the same in every run with the same arguments.
+
+With --full, `roofline` is for the dominant kernel (fused encode + SDF MLP, k_sdf_only): achieved =
 algorithmic flops per launch (F_sdf = 1,049,088 per point) / average launch duration from HIP
 events recorded on the launching stream during the timed steps; peak = 2,500 TFLOP/s (dense bf16 = dense fp16 MFMA).
 --precision mixed (default; the mode get_model ships since round 5): every value that reaches a pixel - sdf, nabla, radiance and
@@ -129,6 +137,29 @@ def launch_plan(n_gpus: int, env: dict, n_devices: int, argv: list, port: int = 
     return "spawn", cmd
 
 
+def dump_outputs(out_dir: str, outputs: dict, budget: int = 64 * 2 ** 20) -> dict:
+    """--dump-outputs: every tensor of `outputs` (other values are skipped) as out_dir/<name>.npy - floating arrays in float32 (float64 stays
+    float64), integer and boolean ones in float64 (exact).  At most `budget` bytes in all: an array larger than its even share of the budget is
+    replaced by a fixed sample of its flattened elements (positions drawn from a generator seeded 0, sorted), the same positions in every run.
+    -> {name: number of elements written}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v for k, v in outputs.items() if torch.is_tensor(v)}
+    share = (budget - 256 * len(arrays)) // max(len(arrays), 1)          # (256 bytes: room for each file's .npy header)
+    written = {}
+    for name, t in arrays.items():
+        dtype = torch.float64 if (t.dtype == torch.float64 or not t.is_floating_point()) else torch.float32
+        a = t.detach().to("cpu", dtype).reshape(-1)
+        if a.numel() * a.element_size() > share:
+            keep = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:share // a.element_size()]
+            a = a[keep.sort().values]
+        else:
+            a = a.reshape(t.shape)
+        np.save(os.path.join(out_dir, name + ".npy"), a.numpy())
+        written[name] = int(a.numel())
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -150,6 +181,9 @@ def main():
     ap.add_argument("--cpu-rays", type=int, default=2048)
     ap.add_argument("--frame", default="480x270", help="HxW of a frame.  480x270 is BASELINE.json's metric (the default and the only size "
                     "the driver's line is quoted on); 960x540 is cfg 5's frame: `--frame 960x540 --steps 90 --shard tiles` is its 90-view loop")
+    ap.add_argument("--full", action="store_true", help="besides the headline: profile the timed steps (roofline, per-kernel ms, algorithmic work of a "
+                    "frame) and run the secondaries and the CPU baseline with its parity checks (off: the plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the arrays the last timed step returned as DIR/<name>.npy")
     args = ap.parse_args()
     global H, W
     H, W = (int(v) for v in args.frame.lower().split("x"))
@@ -225,15 +259,17 @@ def main():
     torch.cuda.synchronize()
 
     def step(s, detailed=False):
+        """-> what the caller receives: render_fn's extras dict (rgb and depth_volume among its arrays) and, at N > 1, the gathered tiles."""
         o, d = rays[s]
         rgb, depth, ex = render_fn(o, d, require_nablas=True, calc_normal=True, detailed_output=detailed, **kw)
         if world > 1:
             tile = torch.cat([rgb[0], depth[0, :, None], ex["normals_volume"][0]], dim=-1)      # [rays, 7]
-            nd.all_gather_tiles(tile)
-        return rgb, ex
+            ex = dict(ex, all_gathered_tiles=nd.all_gather_tiles(tile))
+        return ex
 
+    primary_tiles = args.shard == "tiles" and world > 1
     shared = []                                      # strong mode: every rank holds the SAME frame's rays (rank 0's views)
-    for s_ in range(n_views):
+    for s_ in range(n_views if (primary_tiles or (args.full and world > 1 and not args.no_secondary)) else 0):
         c2w, K = scene.camera(H, W, angle=angles[(s_ * world) % len(angles)])
         o_, d_, _ = rend_util.get_rays(c2w[None].to(dev), K[None].to(dev), H, W)
         shared.append((o_, d_))
@@ -249,7 +285,8 @@ def main():
     rank_times = {}
 
     def timed(fn, profile=False):
-        """W warm-up calls, then exactly K timed ones between barrier + synchronize pairs; max over ranks."""
+        """W warm-up calls, then exactly K timed ones between barrier + synchronize pairs; max over ranks.  -> (seconds, profile, what the
+        last timed call returned)."""
         for s_ in range(args.warmup):
             fn(s_)
         torch.cuda.synchronize()
@@ -258,9 +295,10 @@ def main():
         torch.cuda.synchronize()
         if profile:
             hip.profile_begin()
+        last_ = None
         t0 = time.perf_counter()
         for s_ in range(args.warmup, args.warmup + args.steps):
-            fn(s_)
+            last_ = fn(s_)
         torch.cuda.synchronize()
         t_own = time.perf_counter() - t0              # this rank's own K steps (its collectives included), before it waits for the others
         if dist is not None:
@@ -274,18 +312,21 @@ def main():
             dist.all_gather_object(tall, (dt_, t_own))
             rank_times[fn.__name__] = [t_[1] / args.steps * 1e3 for t_ in tall]
             dt_ = max(t_[0] for t_ in tall)
-        return dt_, prof_
+        return dt_, prof_, last_
 
-    primary_tiles = args.shard == "tiles" and world > 1
-    dt, prof = timed(step_tiles if primary_tiles else step, profile=True)
+    dt, prof, last = timed(step_tiles if primary_tiles else step, profile=args.full)
 
     rays_per_step = H * W * (1 if primary_tiles else world)
     value = rays_per_step * args.steps / dt
 
-    # secondary measurements (never the primary `value`): the other sharding mode at N > 1; the exact-fp32 mode at N = 1
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
+    del last
+
+    # secondary measurements (--full; never the primary `value`): the other sharding mode at N > 1; the exact-fp32 mode at N = 1
     secondary = {}
-    if world > 1 and not args.no_secondary:
-        dt2, _ = timed(step if primary_tiles else step_tiles)
+    if args.full and world > 1 and not args.no_secondary:
+        dt2, _, _ = timed(step if primary_tiles else step_tiles)
         r2 = H * W * (world if primary_tiles else 1)
         secondary["weak_views" if primary_tiles else "strong_tiles"] = {
             "value": round(r2 * args.steps / dt2, 1), "unit": "rays/s", "ms_per_step": round(dt2 / args.steps * 1e3, 2),
@@ -309,7 +350,7 @@ def main():
                                              "scaling": "strong", "what": "ONE 960x540 frame (cfg 5), 2,048-ray tiles round-robin over the ranks + one all_gather"}
     headline_split = args.precision in ("mixed", "bf16x3")
     other = "bf16x3" if args.precision == "mixed" else "mixed"          # the split-bf16 mode that is NOT the headline: a secondary of its own
-    if world == 1 and not args.no_secondary and headline_split:
+    if args.full and world == 1 and not args.no_secondary and headline_split:
         m32, _, f32 = scene.build_model("VolSDF", seed=0, beta=args.beta, device=dev, precision="fp32")
         m32.packed()
         o_, d_ = rays[0]
@@ -534,91 +575,94 @@ def main():
         del ctx3
         torch.cuda.empty_cache()
 
-    # algorithmic work of one of this rank's frames (uses the iter_usage the renderer reports)
-    _, ex = step(args.warmup, detailed=True)
-    torch.cuda.synchronize()
-    usage = ex["iter_usage"][0]
-    rounds = torch.where(usage < 0, torch.full_like(usage, float(kw["max_upsample_steps"])), usage)
-    n_init = 4 * N_SAMPLES
-    flops_frame = float((n_init * (1 + rounds) * F_SDF).sum()) + H * W * (N_SAMPLES + N_IMPORTANCE) * (F_SDF + F_NABLA + F_RAD)
-    hist = {str(int(k)): int(v) for k, v in zip(*[t.tolist() for t in torch.unique(usage, return_counts=True)])}
+    # --full: algorithmic work of a frame, the dominant kernel's roofline and the per-kernel times of the (profiled) timed steps
+    hist = flops_frame = roofline = kernels_ms = None
+    if args.full:
+        # algorithmic work of one of this rank's frames (uses the iter_usage the renderer reports)
+        ex = step(args.warmup, detailed=True)
+        torch.cuda.synchronize()
+        usage = ex["iter_usage"][0]
+        rounds = torch.where(usage < 0, torch.full_like(usage, float(kw["max_upsample_steps"])), usage)
+        n_init = 4 * N_SAMPLES
+        flops_frame = float((n_init * (1 + rounds) * F_SDF).sum()) + H * W * (N_SAMPLES + N_IMPORTANCE) * (F_SDF + F_NABLA + F_RAD)
+        hist = {str(int(k)): int(v) for k, v in zip(*[t.tolist() for t in torch.unique(usage, return_counts=True)])}
 
-    ms, launches, points = prof["k_sdf_only"]
-    roofline = None
-    if launches > 0:
-        flops_per_launch = points / launches * F_SDF
-        avg_s = ms / launches * 1e-3
-        achieved = flops_per_launch / avg_s / 1e12
-        # bf16x3 issues 3 bf16 MFMAs per algorithmic product: priced against the dense bf16 MFMA peak
-        peak = PEAK_F32_MFMA_TFLOPS if args.precision == "fp32" else PEAK_BF16_MFMA_TFLOPS
-        # (mixed: every k_sdf_only launch of a frame is Algorithm 1's - the 2-MFMA kernel, namespace f16x2; the final samples run k_sdf_grad_bf16)
-        kname = {"fp32": "k_sdf_only", "bf16x3": "k_sdf_only_bf16"}.get(args.precision, "f16x1::k_sdf_only_bf16" if calibrated else "f16x2::k_sdf_only_bf16")
-        roofline = {"bound": "mfma", "kernel": kname, "achieved": round(achieved, 2), "peak": peak,
-                    "unit": "TFLOP/s", "frac": round(achieved / peak, 4), "traffic": None,
-                    "launches": int(launches), "avg_launch_ms": round(ms / launches, 4),
-                    "points_per_launch": int(points / launches),
-                    "flops_per_point": F_SDF}
-        if args.precision in ("mixed", "fp16x2"):
-            # ONE fp16 activation term x fp16 hi + lo weight terms: 2 x v_mfma_f32_16x16x32_f16 per product (the dense fp16 peak = the bf16 one)
-            mpp = 1 if calibrated else 2              # (the four k-steps of ready-made encoding units of K2's 59 run three terms in either form)
-            roofline["mfma_per_product"] = mpp
-            roofline["mfma_executed_frac"] = round(mpp * 2.0 * MFMA_MAC_SDF * (points / launches) / avg_s / 1e12 / peak, 4)
-            roofline["ceiling_frac"] = {"matrix_pipe_only": round(0.91 / mpp, 4), "source": "profiles/r02s_ubench_coissue.txt (MFMA-only rate 0.91 of peak)",
-                                        "units": "ALGORITHMIC flops, i.e. comparable with `frac` (a stream of nothing but mfma_per_product-MFMA products reaches 0.91 / mfma_per_product); "
-                                                 "`mfma_executed_frac` (what the matrix pipe executes: mfma_per_product MFMAs per product + tile padding) compares with 0.91 "
-                                                 "(MFMAs alone) and with 0.56 - 0.58 (a synthetic stream of the 3-MFMA kernel's own instruction mix at the power "
-                                                 "cap, profiles/r03u_ubench_power.txt)"}
-            roofline["note"] = ("the sampler's kernel: Algorithm 1's 512 (1 + rounds) SDF queries per ray, 69 % of a bf16x3 frame; frac = ALGORITHMIC flops "
-                                "(F_sdf per point) / launch time / 2,500 TFLOP/s, comparable across modes; the sustained rate is set by the package "
-                                "power cap (joules per product: profiles/r05n power probes), which is why fewer MFMAs per product buy time" +
-                                ("; calibrated sampler: ONE v_mfma_f32_16x16x32_f16 per product over error-compensated one-term weights (csrc/mlp_chain_f16x1.hip, "
-                                 "nerfart_amd/calibrate.py) - with one MFMA per item the kernel's time follows its fragment reads, LDS-DMA pieces and epilogue VALU, not the "
-                                 "matrix pipe; it still draws the package limit, at a 7 % higher clock (profiles/r12_power_k2.json; DESIGN.md 4.1e / 4.1f / 5)" if calibrated else ""))
-        if args.precision == "bf16x3":
-            # what the matrix pipe executes: MFMA_MAC_SDF multiply-adds per point, each as `mfma_per_product` bf16 MFMAs
-            # (hi.hi + hi.lo + lo.hi), as a fraction of the dense bf16 peak
-            roofline["note"] = ("measured limiters (DESIGN.md 4.1b): in isolation, weight bytes moved per column - 1.9 MB of split-bf16 fragments per "
-                                "128-point tile through L2 -> LDS-DMA -> ds_read_b128 (profiles/r02k_ablate_w32.log); in the sustained frame, the "
-                                "package power cap: 1.28 - 1.33 kW of 1.4 kW while rendering, shader clock ~2.1 GHz instead of the 2.4 GHz the "
-                                "peak assumes (profiles/r03l_power_probe.log) - 3 MFMAs per product at ~0.6 of the dense-bf16 rate")
-            # ceilings for this kernel in the same algorithmic-flop units (profiles/r02s_ubench_coissue.txt, tools/ubench_coissue.hip):
-            # 3 MFMAs per product at the measured MFMA-only rate (17.7 nominal cycles per 16x16x32 = 0.91 of peak), and the SIMD's
-            # measured issue capacity for the kernel's own mix of MFMAs, fragment reads, LDS-DMA pieces and epilogue VALU (25.0 cycles)
-            roofline["ceiling_frac"] = {"matrix_pipe_only": round(0.91 / 3, 4), "issue_capacity_for_this_mix": round(0.91 / 3 * 17.7 / 25.0, 4),
-                                        "source": "profiles/r02s_ubench_coissue.txt",
-                                        # a synthetic stream with this kernel's mix (3 MFMAs + 2 ds_read_b128 + ~6 VALU per item, random
-                                        # operands) SUSTAINS 0.562 - 0.577 of the dense-bf16 peak in executed MFMA flops at 1.23 - 1.27 kW;
-                                        # MFMAs alone 0.957 at 1.32 kW (tools/ubench_power.hip) - compare with mfma_executed_frac below
-                                        "sustained_executed_frac_same_mix": 0.577, "sustained_executed_frac_mfma_only": 0.957,
-                                        "source_sustained": "profiles/r03u_ubench_power.txt"}
-            roofline["mfma_per_product"] = 3
-            roofline["mfma_executed_frac"] = round(3 * 2.0 * MFMA_MAC_SDF * (points / launches) / avg_s / 1e12 / peak, 4)
-        # HBM traffic per launch is a PROFILED figure, not measured in this run (bench.py cannot read hardware counters): it
-        # comes from the newest committed PMC summary (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate runs; (2*FETCH +
-        # WRITE) KiB with the gfx950 FETCH_SIZE correction) and is reported as `traffic` only if that profile was taken on
-        # the kernel sources this run executes (source hash recorded by tools/pmc_summary.py); otherwise it is marked stale.
-        import glob
-        # (only profiles of THIS workload: the train-step / CLIP profiles hold the same kernel names at other launch sizes)
-        pm = sorted(f for f in glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_summary.json"))
-                    if not any(t in os.path.basename(f) for t in ("_train_", "_clip_", "_neus_")))
-        if pm:
-            try:
-                js = json.load(open(pm[-1]))
-                kk = js["kernels"][kname]
-                if any("bench.py" not in c or "bench_" in c for c in js.get("commands", [])):
-                    raise ValueError("not a profile of bench.py")
-                from nerfart_amd import volsdf as _volsdf       # (per-launch bytes of the sampler's kernel scale with the rays per chunk)
-                fresh = js.get("csrc_sha256") == hip.csrc_sha256() and js.get("default_rayschunk") == _volsdf.DEFAULT_RAYSCHUNK
-                roofline["traffic_profiled"] = {"bytes_per_launch": int(kk["hbm_bytes_corrected_per_launch"]), "source": os.path.basename(pm[-1]),
-                                                "profile_csrc_sha256": js.get("csrc_sha256"), "matches_this_build": fresh,
-                                                "mfma_busy_pmc": round(kk.get("mfma_util", 0.0), 4)}
-                roofline["traffic"] = int(kk["hbm_bytes_corrected_per_launch"]) if fresh else None
-            except Exception:
-                pass
-    kernels_ms = {k: round(v[0] / args.steps, 3) for k, v in prof.items() if k != "k_wgrad256"}
+        ms, launches, points = prof["k_sdf_only"]
+        roofline = None
+        if launches > 0:
+            flops_per_launch = points / launches * F_SDF
+            avg_s = ms / launches * 1e-3
+            achieved = flops_per_launch / avg_s / 1e12
+            # bf16x3 issues 3 bf16 MFMAs per algorithmic product: priced against the dense bf16 MFMA peak
+            peak = PEAK_F32_MFMA_TFLOPS if args.precision == "fp32" else PEAK_BF16_MFMA_TFLOPS
+            # (mixed: every k_sdf_only launch of a frame is Algorithm 1's - the 2-MFMA kernel, namespace f16x2; the final samples run k_sdf_grad_bf16)
+            kname = {"fp32": "k_sdf_only", "bf16x3": "k_sdf_only_bf16"}.get(args.precision, "f16x1::k_sdf_only_bf16" if calibrated else "f16x2::k_sdf_only_bf16")
+            roofline = {"bound": "mfma", "kernel": kname, "achieved": round(achieved, 2), "peak": peak,
+                        "unit": "TFLOP/s", "frac": round(achieved / peak, 4), "traffic": None,
+                        "launches": int(launches), "avg_launch_ms": round(ms / launches, 4),
+                        "points_per_launch": int(points / launches),
+                        "flops_per_point": F_SDF}
+            if args.precision in ("mixed", "fp16x2"):
+                # ONE fp16 activation term x fp16 hi + lo weight terms: 2 x v_mfma_f32_16x16x32_f16 per product (the dense fp16 peak = the bf16 one)
+                mpp = 1 if calibrated else 2              # (the four k-steps of ready-made encoding units of K2's 59 run three terms in either form)
+                roofline["mfma_per_product"] = mpp
+                roofline["mfma_executed_frac"] = round(mpp * 2.0 * MFMA_MAC_SDF * (points / launches) / avg_s / 1e12 / peak, 4)
+                roofline["ceiling_frac"] = {"matrix_pipe_only": round(0.91 / mpp, 4), "source": "profiles/r02s_ubench_coissue.txt (MFMA-only rate 0.91 of peak)",
+                                            "units": "ALGORITHMIC flops, i.e. comparable with `frac` (a stream of nothing but mfma_per_product-MFMA products reaches 0.91 / mfma_per_product); "
+                                                     "`mfma_executed_frac` (what the matrix pipe executes: mfma_per_product MFMAs per product + tile padding) compares with 0.91 "
+                                                     "(MFMAs alone) and with 0.56 - 0.58 (a synthetic stream of the 3-MFMA kernel's own instruction mix at the power "
+                                                     "cap, profiles/r03u_ubench_power.txt)"}
+                roofline["note"] = ("the sampler's kernel: Algorithm 1's 512 (1 + rounds) SDF queries per ray, 69 % of a bf16x3 frame; frac = ALGORITHMIC flops "
+                                    "(F_sdf per point) / launch time / 2,500 TFLOP/s, comparable across modes; the sustained rate is set by the package "
+                                    "power cap (joules per product: profiles/r05n power probes), which is why fewer MFMAs per product buy time" +
+                                    ("; calibrated sampler: ONE v_mfma_f32_16x16x32_f16 per product over error-compensated one-term weights (csrc/mlp_chain_f16x1.hip, "
+                                     "nerfart_amd/calibrate.py) - with one MFMA per item the kernel's time follows its fragment reads, LDS-DMA pieces and epilogue VALU, not the "
+                                     "matrix pipe; it still draws the package limit, at a 7 % higher clock (profiles/r12_power_k2.json; DESIGN.md 4.1e / 4.1f / 5)" if calibrated else ""))
+            if args.precision == "bf16x3":
+                # what the matrix pipe executes: MFMA_MAC_SDF multiply-adds per point, each as `mfma_per_product` bf16 MFMAs
+                # (hi.hi + hi.lo + lo.hi), as a fraction of the dense bf16 peak
+                roofline["note"] = ("measured limiters (DESIGN.md 4.1b): in isolation, weight bytes moved per column - 1.9 MB of split-bf16 fragments per "
+                                    "128-point tile through L2 -> LDS-DMA -> ds_read_b128 (profiles/r02k_ablate_w32.log); in the sustained frame, the "
+                                    "package power cap: 1.28 - 1.33 kW of 1.4 kW while rendering, shader clock ~2.1 GHz instead of the 2.4 GHz the "
+                                    "peak assumes (profiles/r03l_power_probe.log) - 3 MFMAs per product at ~0.6 of the dense-bf16 rate")
+                # ceilings for this kernel in the same algorithmic-flop units (profiles/r02s_ubench_coissue.txt, tools/ubench_coissue.hip):
+                # 3 MFMAs per product at the measured MFMA-only rate (17.7 nominal cycles per 16x16x32 = 0.91 of peak), and the SIMD's
+                # measured issue capacity for the kernel's own mix of MFMAs, fragment reads, LDS-DMA pieces and epilogue VALU (25.0 cycles)
+                roofline["ceiling_frac"] = {"matrix_pipe_only": round(0.91 / 3, 4), "issue_capacity_for_this_mix": round(0.91 / 3 * 17.7 / 25.0, 4),
+                                            "source": "profiles/r02s_ubench_coissue.txt",
+                                            # a synthetic stream with this kernel's mix (3 MFMAs + 2 ds_read_b128 + ~6 VALU per item, random
+                                            # operands) SUSTAINS 0.562 - 0.577 of the dense-bf16 peak in executed MFMA flops at 1.23 - 1.27 kW;
+                                            # MFMAs alone 0.957 at 1.32 kW (tools/ubench_power.hip) - compare with mfma_executed_frac below
+                                            "sustained_executed_frac_same_mix": 0.577, "sustained_executed_frac_mfma_only": 0.957,
+                                            "source_sustained": "profiles/r03u_ubench_power.txt"}
+                roofline["mfma_per_product"] = 3
+                roofline["mfma_executed_frac"] = round(3 * 2.0 * MFMA_MAC_SDF * (points / launches) / avg_s / 1e12 / peak, 4)
+            # HBM traffic per launch is a PROFILED figure, not measured in this run (bench.py cannot read hardware counters): it
+            # comes from the newest committed PMC summary (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate runs; (2*FETCH +
+            # WRITE) KiB with the gfx950 FETCH_SIZE correction) and is reported as `traffic` only if that profile was taken on
+            # the kernel sources this run executes (source hash recorded by tools/pmc_summary.py); otherwise it is marked stale.
+            import glob
+            # (only profiles of THIS workload: the train-step / CLIP profiles hold the same kernel names at other launch sizes)
+            pm = sorted(f for f in glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_summary.json"))
+                        if not any(t in os.path.basename(f) for t in ("_train_", "_clip_", "_neus_")))
+            if pm:
+                try:
+                    js = json.load(open(pm[-1]))
+                    kk = js["kernels"][kname]
+                    if any("bench.py" not in c or "bench_" in c for c in js.get("commands", [])):
+                        raise ValueError("not a profile of bench.py")
+                    from nerfart_amd import volsdf as _volsdf       # (per-launch bytes of the sampler's kernel scale with the rays per chunk)
+                    fresh = js.get("csrc_sha256") == hip.csrc_sha256() and js.get("default_rayschunk") == _volsdf.DEFAULT_RAYSCHUNK
+                    roofline["traffic_profiled"] = {"bytes_per_launch": int(kk["hbm_bytes_corrected_per_launch"]), "source": os.path.basename(pm[-1]),
+                                                    "profile_csrc_sha256": js.get("csrc_sha256"), "matches_this_build": fresh,
+                                                    "mfma_busy_pmc": round(kk.get("mfma_util", 0.0), 4)}
+                    roofline["traffic"] = int(kk["hbm_bytes_corrected_per_launch"]) if fresh else None
+                except Exception:
+                    pass
+        kernels_ms = {k: round(v[0] / args.steps, 3) for k, v in prof.items() if k != "k_wgrad256"}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import render as orender
         try:
             import psutil
@@ -782,15 +826,15 @@ def main():
                                    "secondary.mixed_as_get_model_ships: the mode as get_model returns it (2-MFMA sampler: what a training step runs)"},
                        "sampler_guard": None if not getattr(model, "sampler_guard", 0.0) else {
                            "guard": model.sampler_guard, "late_round": model.sampler_late_round, "rays_sampled_twice_frac": round(model.render_stats.get("escalated", 0) / max(model.render_stats.get("rays", 1), 1), 5),
-                           "second_run_sdf_ms_per_step": round(prof["k_sdf_only_escalation"][0] / args.steps, 3),
-                           "second_run_sdf_points_per_step": int(prof["k_sdf_only_escalation"][2] / args.steps),
+                           "second_run_sdf_ms_per_step": round(prof["k_sdf_only_escalation"][0] / args.steps, 3) if prof else None,
+                           "second_run_sdf_points_per_step": int(prof["k_sdf_only_escalation"][2] / args.steps) if prof else None,
                            "what": "mixed mode: rays whose convergence decision in Algorithm 1 lies within guard * eps of eps, rays that never converge and rays still "
                                    "active after up-sampling round `late_round` are sampled again on the split-bf16 kernels (nerfart_volsdf_fine_sample_guarded2); share "
                                    "over every render call of this run"},
                        "samples_per_sec": round(value * (N_SAMPLES + N_IMPORTANCE), 1),
                        "iter_usage_hist": hist,
-                       "algorithmic_tflop_per_frame": round(flops_frame / 1e12, 2),
-                       "end_to_end_tflops": round(flops_frame * (1 if primary_tiles else world) * args.steps / dt / 1e12, 2),
+                       "algorithmic_tflop_per_frame": None if flops_frame is None else round(flops_frame / 1e12, 2),
+                       "end_to_end_tflops": None if flops_frame is None else round(flops_frame * (1 if primary_tiles else world) * args.steps / dt / 1e12, 2),
                        "mlp_kernel_ms_per_step": kernels_ms,
                        "ref_3090_rays_per_s": 6480},
             "roofline": roofline,

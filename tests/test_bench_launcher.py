@@ -72,3 +72,26 @@ def test_the_multi_gpu_line_explains_itself():
     json.dumps(f); json.dumps(g)
     name, line = b.cached_n1_line()
     assert name is None or (line["n_gpus"] == 1 and line["value"] > 0)
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path):
+    """--dump-outputs: every tensor of what the timed step returned becomes <name>.npy in float32 (integer / boolean / float64 arrays in
+    float64, exact); non-tensors are skipped; an array past its share of the byte budget is replaced by the same seeded sample in every run."""
+    import numpy as np
+    import torch
+    b = _bench()
+    g = torch.Generator().manual_seed(3)
+    out = {"rgb": torch.rand(1, 600, 3, generator=g), "depth_volume": torch.rand(1, 600, generator=g).half(),
+           "iter_usage": torch.randint(-1, 7, (1, 600), generator=g, dtype=torch.int32), "mask": torch.rand(1, 600, generator=g) > 0.5, "alpha": None}
+    written = b.dump_outputs(str(tmp_path / "a"), out)
+    assert sorted(written) == ["depth_volume", "iter_usage", "mask", "rgb"] and sorted(os.listdir(tmp_path / "a")) == [k + ".npy" for k in sorted(written)]
+    rgb, usage = np.load(tmp_path / "a" / "rgb.npy"), np.load(tmp_path / "a" / "iter_usage.npy")
+    assert rgb.dtype == np.float32 and rgb.shape == (1, 600, 3) and np.array_equal(rgb, out["rgb"].numpy())
+    assert usage.dtype == np.float64 and np.array_equal(usage, out["iter_usage"].numpy().astype(np.float64))
+    assert np.load(tmp_path / "a" / "depth_volume.npy").dtype == np.float32 and np.load(tmp_path / "a" / "mask.npy").dtype == np.float64
+    small = 4 * 4096
+    w1, w2 = b.dump_outputs(str(tmp_path / "b"), out, budget=small), b.dump_outputs(str(tmp_path / "c"), out, budget=small)
+    assert w1 == w2 and w1["rgb"] < 1800
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= small
+    s1, s2 = np.load(tmp_path / "b" / "rgb.npy"), np.load(tmp_path / "c" / "rgb.npy")
+    assert np.array_equal(s1, s2) and np.isin(s1, out["rgb"].numpy().reshape(-1)).all()

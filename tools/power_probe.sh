@@ -7,7 +7,7 @@ REPO=$(pwd); TAG=$1; OUT=$REPO/gpurun_out; mkdir -p $OUT
 for var in v1 w32; do
   ( for i in $(seq 1 60); do rocm-smi --showpower --showclocks 2>/dev/null | grep -E "Power|sclk" | tr '\n' ' '; echo; sleep 0.2; done ) > $OUT/${TAG}_smi_$var.txt &
   SMI=$!
-  NERFART_K2=$var python bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-secondary > $OUT/${TAG}_bench_$var.json 2> /dev/null
+  NERFART_K2=$var python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-secondary > $OUT/${TAG}_bench_$var.json 2> /dev/null
   kill $SMI 2>/dev/null; wait $SMI 2>/dev/null
   python - <<PY
 import json,re

@@ -8,7 +8,7 @@ REPO=$(pwd); TAG=$1; OUT=$REPO/gpurun_out; mkdir -p $OUT
 for prec in ${PRECS:-mixed bf16x3 fp16x2}; do
   ( for i in $(seq 1 80); do rocm-smi --showpower --showclocks 2>/dev/null | grep -E "Power|sclk" | tr '\n' ' '; echo; sleep 0.2; done ) > $OUT/${TAG}_smi_$prec.txt &
   SMI=$!
-  python bench.py --precision $prec --steps 10 --warmup 2 --no-cpu-baseline --no-secondary > $OUT/${TAG}_bench_$prec.json 2> /dev/null
+  python bench.py --full --precision $prec --steps 10 --warmup 2 --no-cpu-baseline --no-secondary > $OUT/${TAG}_bench_$prec.json 2> /dev/null
   kill $SMI 2>/dev/null; wait $SMI 2>/dev/null
   python - <<PY
 import json,re

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Run on the GPU box:  bash tools/profile_bench.sh <tag> [bench args...]
-#   1. plain bench line                        -> gpurun_out/<tag>_bench_line.json
+#   1. the bench line of bench.py --full       -> $OUT/<tag>_bench_line.json
 #   2. rocprofv3 --kernel-trace --stats        -> gpurun_out/<tag>_bench_kernel_stats.txt (+ the bench line under rocprof)
 #   3. rocprofv3 --pmc passes (separate runs)  -> gpurun_out/<tag>_pmc_<set>.txt, gpurun_out/<tag>_pmc_summary.json
 # Only text summaries leave the box (the .db files stay in /tmp).
@@ -10,7 +10,7 @@ TAG=$1; shift
 ARGS="$@"
 OUT=$REPO/gpurun_out
 mkdir -p $OUT
-python bench.py $ARGS > $OUT/${TAG}_bench_line.json 2> $OUT/${TAG}_bench.err
+python bench.py --full $ARGS > $OUT/${TAG}_bench_line.json 2> $OUT/${TAG}_bench.err
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/kt && timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/kt -o r -- python $REPO/bench.py $ARGS --no-cpu-baseline --no-secondary > $OUT/${TAG}_bench_line_under_rocprof.json 2> /tmp/kt.err
 db=$(find /tmp/kt -name "*.db" | head -1)
