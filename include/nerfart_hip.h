@@ -148,7 +148,8 @@ int nerfart_linspace_depths(const float* t_dev, int n, const float* near, const 
 
 /* ---- VolSDF sampler stages (models/frameworks/volsdf.py fine_sample :97-302; error_bound :56-94;
  * utils/rend_util.py sample_pdf :256-293, sample_cdf :295-328).  Exposed one by one for parity tests;
- * nerfart_volsdf_fine_sample chains them. */
+ * nerfart_volsdf_fine_sample chains them.  Rows of n samples at row stride cap: n < 2, n > cap and (merge_check) n + n_up > cap are
+ * refused with 2 before any HIP call. */
 int nerfart_volsdf_first_check(int n_rays, int n, int cap, int n_final, float eps, float alpha_net, float beta_net,
                                const float* dA, const float* sA, const float* u_final, int u_final_stride,
                                float beta_plus0_denom, const float* far, float far_s, float* d_fine, float* beta_plus,

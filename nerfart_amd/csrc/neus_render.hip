@@ -203,6 +203,7 @@ static int upsample_step(bool direct, int n_rays, int n, int cap, int n_new, flo
                          const float* u_new, int u_new_stride, float* d_new, void* stream) {
     if (n_rays <= 0) return 0;
     if (n < 2 || n_new < 1) { set_last_error("neus upsample: needs n >= 2 bins and n_new >= 1"); return 2; }
+    if (n > cap) { set_last_error("neus upsample: n bins exceed the row stride cap"); return 2; }
     if (n_new > 64 && (n_new & (n_new - 1))) { set_last_error("neus upsample: n_new must be <= 64 or a power of two"); return 2; }
     const int npad = n_new < 64 ? 64 : n_new;
     const size_t lds = ((size_t)4 * n + npad) * sizeof(float);

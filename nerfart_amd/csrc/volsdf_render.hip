@@ -374,6 +374,18 @@ int nerfart_linspace_depths(const float* t_dev, int n, const float* near, const 
     return 0;
 }
 
+// The exported stage entry points take a row stride `cap` from the caller: a row length they could not hold is refused before any HIP call,
+// after the empty launch returns 0 as before (the order of neus_render.hip's upsample_step).  The internal calls of fine_sample_run size cap
+// themselves and go straight to the *_launch functions.
+static int check_rows(const char* who, int n, int cap, int n_extra) {
+    char msg[160];
+    if (n < 2 || n > cap) snprintf(msg, sizeof(msg), "%s: needs 2 <= n <= cap (n = %d, cap = %d)", who, n, cap);
+    else if ((long long)n + n_extra > cap) snprintf(msg, sizeof(msg), "%s: n + n_up = %lld exceeds the row capacity cap = %d", who, (long long)n + n_extra, cap);
+    else return 0;
+    set_last_error(msg);
+    return 2;
+}
+
 static int set_lds(const void* k, size_t bytes) {
     if (bytes > 160 * 1024) { set_last_error("per-ray kernel needs more than 160 KiB of LDS (too many samples per ray)"); return 2; }
     NERFART_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
@@ -400,12 +412,14 @@ int nerfart_volsdf_first_check(int n_rays, int n, int cap, int n_final, float ep
                                const float* dA, const float* sA, const float* u_final, int u_final_stride,
                                float beta_plus0_denom, const float* far, float far_s, float* d_fine, float* beta_plus,
                                float* beta_map, float* iter_usage, int* act_out, int* act_count, void* stream) {
+    if (n_rays <= 0) return 0;
+    if (int rc = check_rows("volsdf_first_check", n, cap, 0)) return rc;
     return first_check_launch(n_rays, n, cap, n_final, eps, alpha_net, beta_net, dA, sA, u_final, u_final_stride, beta_plus0_denom, far, far_s, d_fine,
                               beta_plus, beta_map, iter_usage, act_out, act_count, 0.f, nullptr, nullptr, stream);
 }
 
-int nerfart_volsdf_upsample(int n_active, int n, int cap, int n_up, const float* dA, const float* sA, const int* act,
-                            const float* beta_plus, const float* u_up, int clamp_bounds, float* d_new, void* stream) {
+static int upsample_launch(int n_active, int n, int cap, int n_up, const float* dA, const float* sA, const int* act,
+                           const float* beta_plus, const float* u_up, int clamp_bounds, float* d_new, void* stream) {
     if (n_active <= 0) return 0;
     if (n_up & (n_up - 1)) { set_last_error("n_up must be a power of two"); return 2; }
     SamplerParams P{n, cap, n_up, 0, 0, 0, 0.f, 0.f, 0.f};
@@ -415,6 +429,13 @@ int nerfart_volsdf_upsample(int n_active, int n, int cap, int n_up, const float*
                        clamp_bounds, d_new);
     NERFART_HIP(hipGetLastError());
     return 0;
+}
+
+int nerfart_volsdf_upsample(int n_active, int n, int cap, int n_up, const float* dA, const float* sA, const int* act,
+                            const float* beta_plus, const float* u_up, int clamp_bounds, float* d_new, void* stream) {
+    if (n_active <= 0) return 0;
+    if (int rc = check_rows("volsdf_upsample", n, cap, 0)) return rc;
+    return upsample_launch(n_active, n, cap, n_up, dA, sA, act, beta_plus, u_up, clamp_bounds, d_new, stream);
 }
 
 static int merge_check_launch(int n_active, int n, int cap, int n_up, int n_final, int max_bisect, int it, float eps,
@@ -437,13 +458,15 @@ int nerfart_volsdf_merge_check(int n_active, int n, int cap, int n_up, int n_fin
                                const int* act, const float* d_new, const float* s_new, const float* u_final,
                                int u_final_stride, float* d_fine, float* beta_plus, float* beta_map, float* iter_usage,
                                int* act_out, int* act_count, void* stream) {
+    if (n_active <= 0) return 0;
+    if (int rc = check_rows("volsdf_merge_check", n, cap, n_up)) return rc;
     return merge_check_launch(n_active, n, cap, n_up, n_final, max_bisect, it, eps, alpha_net, beta_net, dA, sA, dB, sB, act, d_new, s_new, u_final,
                               u_final_stride, d_fine, beta_plus, beta_map, iter_usage, act_out, act_count, 0.f, nullptr, nullptr, stream);
 }
 
-int nerfart_volsdf_finalize(int n_active, int n, int cap, int n_final, const float* dA, const float* sA, const int* act,
-                            const float* u_final, int u_final_stride, const float* beta_plus, float* d_fine,
-                            float* beta_map, float* iter_usage, void* stream) {
+static int finalize_launch(int n_active, int n, int cap, int n_final, const float* dA, const float* sA, const int* act,
+                           const float* u_final, int u_final_stride, const float* beta_plus, float* d_fine,
+                           float* beta_map, float* iter_usage, void* stream) {
     if (n_active <= 0) return 0;
     SamplerParams P{n, cap, 0, n_final, 0, 0, 0.f, 0.f, 0.f, u_final_stride};
     const size_t lds = (size_t)3 * n * sizeof(float);
@@ -452,6 +475,14 @@ int nerfart_volsdf_finalize(int n_active, int n, int cap, int n_final, const flo
                        u_final, beta_plus, d_fine, beta_map, iter_usage);
     NERFART_HIP(hipGetLastError());
     return 0;
+}
+
+int nerfart_volsdf_finalize(int n_active, int n, int cap, int n_final, const float* dA, const float* sA, const int* act,
+                            const float* u_final, int u_final_stride, const float* beta_plus, float* d_fine,
+                            float* beta_map, float* iter_usage, void* stream) {
+    if (n_active <= 0) return 0;
+    if (int rc = check_rows("volsdf_finalize", n, cap, 0)) return rc;
+    return finalize_launch(n_active, n, cap, n_final, dA, sA, act, u_final, u_final_stride, beta_plus, d_fine, beta_map, iter_usage, stream);
 }
 
 int nerfart_sort_concat(int n_rays, const float* a, int na, int a_stride, const float* b, int nb, int b_stride,
@@ -590,7 +621,7 @@ static int fine_sample_run(const float* surf_blob, int precision, const float* e
     int *act = w.act0, *act_next = w.act1;
     int n = n_init;
     for (int it = 1; it <= max_iter && n_act > 0; ++it) {
-        if (int rc = nerfart_volsdf_upsample(n_act, n, cap, n_up, dA, sA, act, w.beta_plus, w.u_up, it > 1, w.d_new, stream)) return rc;
+        if (int rc = upsample_launch(n_act, n, cap, n_up, dA, sA, act, w.beta_plus, w.u_up, it > 1, w.d_new, stream)) return rc;
         if (int rc = nerfart_sdf_fwd_rays(surf_blob, precision, rays_o, rays_dn, act, w.d_new, n_act, n_up, n_up, R_bg, w.s_new, n_up, stream)) return rc;
         if (int rc = merge_check_launch(n_act, n, cap, n_up, n_final, max_bisect, it, eps, alpha_net, beta_net, dA, sA,
                                         dB, sB, act, w.d_new, w.s_new, w.u_final, u_stride, d_fine, w.beta_plus,
@@ -607,8 +638,8 @@ static int fine_sample_run(const float* surf_blob, int precision, const float* e
     }
     if (!guarded) {
         if (n_act > 0)
-            if (int rc = nerfart_volsdf_finalize(n_act, n, cap, n_final, dA, sA, act, w.u_final, u_stride, w.beta_plus, d_fine,
-                                                 beta_map, iter_usage, stream)) return rc;
+            if (int rc = finalize_launch(n_act, n, cap, n_final, dA, sA, act, w.u_final, u_stride, w.beta_plus, d_fine,
+                                         beta_map, iter_usage, stream)) return rc;
         return 0;
     }
     // ---- escalation: the guard-band rays listed so far + the rays that never converged -> Algorithm 1 again, on the escalation blob ----

@@ -172,3 +172,41 @@ def test_direct_more_refuses_a_bin_count_that_cannot_fit_the_lds():
     args = lambda nn: [null, null, 1, 3, null, null, 8, 1.0, 64.0, 64, 64, 4, 2, nn, 1 / 64., 0, 8192] + [null] * 3 + [0] + [null] * 12 + [null, 0, null]
     assert hip.lib.nerfart_neus_render_algo_fwd(*args(20000)) != 0 and "10,200" in hip.lib.nerfart_last_error().decode()
     assert hip.lib.nerfart_neus_render_algo_fwd(*args(2048)) != 0 and "10,200" not in hip.lib.nerfart_last_error().decode()      # passes THIS check (then: no workspace)
+
+
+def test_stage_entry_points_refuse_rows_that_do_not_fit_their_stride():
+    """The exported per-ray stage entry points take the row stride `cap` from the caller: n < 2, n > cap and (merge check) n + n_up > cap are refused
+    with a message before any HIP call - here with null buffers, so nothing is launched."""
+    import ctypes as C
+    from nerfart_amd import hip
+    lib, null = hip.lib, C.c_void_p(0)
+
+    def err():
+        return lib.nerfart_last_error().decode()
+
+    def first_check(n, cap):
+        return lib.nerfart_volsdf_first_check(1, n, cap, 64, 0.1, 100.0, 0.01, null, null, null, 0, 1.0, null, 6.0, null, null, null, null, null, null, null)
+
+    def upsample(n, cap):
+        return lib.nerfart_volsdf_upsample(1, n, cap, 512, null, null, null, null, null, 1, null, null)
+
+    def merge_check(n, cap, n_up):
+        return lib.nerfart_volsdf_merge_check(1, n, cap, n_up, 64, 10, 1, 0.1, 100.0, 0.01, null, null, null, null, null, null, null, null, 0,
+                                              null, null, null, null, null, null, null)
+
+    def finalize(n, cap):
+        return lib.nerfart_volsdf_finalize(1, n, cap, 64, null, null, null, null, 0, null, null, null, null, null)
+
+    for name, call in (("volsdf_first_check", first_check), ("volsdf_upsample", upsample), ("volsdf_finalize", finalize),
+                       ("volsdf_merge_check", lambda n, cap: merge_check(n, cap + 512, 512))):
+        for n, cap in ((1, 512), (0, 512), (513, 512), (4096, 2048)):
+            assert call(n, cap) == 2, (name, n, cap)
+            assert name in err() and "cap" in err(), err()
+    assert lib.nerfart_volsdf_upsample(0, 1, 0, 512, null, null, null, null, null, 1, null, null) == 0     # an empty launch stays a no-op
+    assert lib.nerfart_volsdf_finalize(0, 0, 0, 64, null, null, null, null, 0, null, null, null, null, null) == 0
+    assert merge_check(512, 1023, 512) == 2 and "exceeds the row capacity" in err()
+    assert merge_check(1536, 2047, 512) == 2 and "exceeds the row capacity" in err()
+    for direct in (0, 1):
+        step = lib.nerfart_neus_direct_upsample_step if direct else lib.nerfart_neus_upsample_step
+        assert step(1, 65, 64, 16, 64.0, null, null, null, 0, null, null) == 2 and "cap" in err()
+        assert step(1, 1, 64, 16, 64.0, null, null, null, 0, null, null) == 2 and "n >= 2" in err()
