@@ -208,7 +208,8 @@ int nerfart_volsdf_fine_sample_guarded2(const float* surf_blob, int precision, c
 int nerfart_sort_concat(int n_rays, const float* a, int na, int a_stride, const float* b, int nb, int b_stride,
                         float* out, int out_stride, void* stream);
 
-/* sdf_to_sigma + ray integration (volsdf.py:34-53, :544-576).  normals / sigma_out / p_out / tau_out may be NULL. */
+/* sdf_to_sigma + ray integration (volsdf.py:34-53, :544-576).  normals / sigma_out / p_out / tau_out may be NULL; normals needs nabla.
+ * P samples per ray are P - 1 intervals: P >= 2 (any length above that); P < 2 is refused with 2 before any HIP call. */
 int nerfart_volsdf_composite(int n_rays, int P, const float* d_all, const float* sdf, const float* radiance,
                              const float* nabla, float alpha, float beta, int white_bkgd, float* rgb, float* depth,
                              float* acc, float* normals, float* sigma_out, float* p_out, float* tau_out, void* stream);
@@ -217,13 +218,15 @@ int nerfart_volsdf_composite(int n_rays, int P, const float* d_all, const float*
  * (g_acc [R] or NULL: the cotangent of mask_volume, the mask BCE of the reconstruction objective, neus.py:600-603):
  * g_rgb [R,3] -> g_sdf [R,P] (through sdf_to_sigma, volsdf.py:34-53), g_rad [R,P,3], and
  * g_alpha_beta[2] += (d loss / d alpha, d loss / d beta) (accumulated with atomics: zero it first; may be NULL).
- * What `rgb.backward(gradient)` (volsdf.py:766) does to the per-ray stage; first hand-written piece of B1 "bwd". */
+ * What `rgb.backward(gradient)` (volsdf.py:766) does to the per-ray stage; first hand-written piece of B1 "bwd".
+ * 2 <= P <= 513 (a lane holds at most 8 intervals in registers); any other P is refused with 2 before any HIP call. */
 int nerfart_volsdf_composite_bwd(int n_rays, int P, const float* d_all, const float* sdf, const float* radiance, float alpha,
                                  float beta, int white_bkgd, const float* g_rgb, const float* g_acc, float* g_sdf, float* g_rad,
                                  float* g_alpha_beta, void* stream);
 
 /* The same for NeuS (neus.py:29-78, :373-395): sdf [R,P] at the samples, radiance [R,P-1,3] at the mid-points, s =
- * exp(ln_s * speed_factor) -> g_sdf [R,P], g_rad_mid [R,P-1,3], g_s[0] += d loss / d s. */
+ * exp(ln_s * speed_factor) -> g_sdf [R,P], g_rad_mid [R,P-1,3], g_s[0] += d loss / d s (accumulated with atomics: zero it first; may be NULL).
+ * 2 <= P <= 513, as nerfart_volsdf_composite_bwd; any other P is refused with 2 before any HIP call. */
 int nerfart_neus_composite_bwd(int n_rays, int P, const float* sdf, const float* rad_mid, float s, int white_bkgd, const float* g_rgb,
                                const float* g_acc, float* g_sdf, float* g_rad_mid, float* g_s, void* stream);
 
@@ -283,6 +286,7 @@ int nerfart_neus_upsample_step(int n_rays, int n, int cap, int n_new, float inv_
                                const float* u_new, int u_new_stride, float* d_new, void* stream);
 int nerfart_merge_sorted_pairs(int n_rays, int n, int cap, int n_new, float* d, float* sdf, const float* d_new,
                                const float* s_new, void* stream);
+/* NeuS ray integration (neus.py:322, :373-395): P >= 2 as nerfart_volsdf_composite (P < 2 is refused with 2); every output after acc may be NULL. */
 int nerfart_neus_composite(int n_rays, int P, const float* d_all, const float* sdf, const float* radiance_mid,
                            const float* nabla, float s, int white_bkgd, float* rgb, float* depth, float* acc,
                            float* normals, float* cdf_out, float* alpha_out, float* w_out, float* d_mid_out,

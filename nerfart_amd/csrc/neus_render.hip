@@ -241,6 +241,7 @@ int nerfart_neus_composite(int n_rays, int P, const float* d_all, const float* s
                            float* normals, float* cdf_out, float* alpha_out, float* w_out, float* d_mid_out,
                            void* stream) {
     if (n_rays <= 0) return 0;
+    if (P < 2) { set_last_error("neus_composite: needs P >= 2 samples per ray (P - 1 intervals)"); return 2; }
     if (normals && !nabla) { set_last_error("composite: normals requested without nablas"); return 2; }
     hipLaunchKernelGGL(k_composite_neus, dim3(n_rays), dim3(64), 0, (hipStream_t)stream, P, d_all, sdf, radiance_mid, nabla, s,
                        white_bkgd, rgb, depth, acc, normals, cdf_out, alpha_out, w_out, d_mid_out);

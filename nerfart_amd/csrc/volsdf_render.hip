@@ -501,6 +501,7 @@ int nerfart_volsdf_composite(int n_rays, int P, const float* d_all, const float*
                              const float* nabla, float alpha, float beta, int white_bkgd, float* rgb, float* depth,
                              float* acc, float* normals, float* sigma_out, float* p_out, float* tau_out, void* stream) {
     if (n_rays <= 0) return 0;
+    if (P < 2) { set_last_error("volsdf_composite: needs P >= 2 samples per ray (P - 1 intervals)"); return 2; }
     if (normals && !nabla) { set_last_error("composite: normals requested without nablas"); return 2; }
     hipLaunchKernelGGL(k_composite_volsdf, dim3(n_rays), dim3(64), 0, (hipStream_t)stream, P, d_all, sdf, radiance, nabla,
                        alpha, beta, white_bkgd, rgb, depth, acc, normals, sigma_out, p_out, tau_out);

@@ -210,3 +210,37 @@ def test_stage_entry_points_refuse_rows_that_do_not_fit_their_stride():
         step = lib.nerfart_neus_direct_upsample_step if direct else lib.nerfart_neus_upsample_step
         assert step(1, 65, 64, 16, 64.0, null, null, null, 0, null, null) == 2 and "cap" in err()
         assert step(1, 1, 64, 16, 64.0, null, null, null, 0, null, null) == 2 and "n >= 2" in err()
+
+
+def test_composite_entry_points_refuse_rows_without_an_interval():
+    """nerfart_volsdf_composite / nerfart_neus_composite integrate P - 1 intervals: P < 2 is refused with a message after the empty-launch return and
+    before any HIP call (with P <= 0 and the detail outputs set, lane 0 would read and write outside the row) - here with null buffers.  The two
+    backwards refuse P < 2 and P > 513 the same way."""
+    import ctypes as C
+    from nerfart_amd import hip
+    lib, null = hip.lib, C.c_void_p(0)
+
+    def err():
+        return lib.nerfart_last_error().decode()
+
+    def volsdf(n_rays, P):
+        return lib.nerfart_volsdf_composite(n_rays, P, null, null, null, null, 100.0, 0.01, 0, null, null, null, null, null, null, null, null)
+
+    def neus(n_rays, P):
+        return lib.nerfart_neus_composite(n_rays, P, null, null, null, null, 64.0, 0, null, null, null, null, null, null, null, null, null)
+
+    def volsdf_bwd(n_rays, P):
+        return lib.nerfart_volsdf_composite_bwd(n_rays, P, null, null, null, 100.0, 0.01, 0, null, null, null, null, null, null)
+
+    def neus_bwd(n_rays, P):
+        return lib.nerfart_neus_composite_bwd(n_rays, P, null, null, 64.0, 0, null, null, null, null, null, null)
+
+    for name, call in (("volsdf_composite", volsdf), ("neus_composite", neus)):
+        for P in (1, 0, -1, -2147483647):
+            assert call(1, P) == 2, (name, P)
+            assert name in err() and "P >= 2" in err(), err()
+        assert call(0, 0) == 0 and call(0, 192) == 0 and call(-1, 1) == 0           # an empty launch stays a no-op
+    for call in (volsdf_bwd, neus_bwd):
+        for P in (1, 0, 514, 1025):
+            assert call(1, P) == 2 and "2 <= P <= 513" in err(), (P, err())
+        assert call(0, 0) == 0

@@ -83,7 +83,7 @@ def test_neus_pass2_radiance_frozen():
 
 @pytest.mark.parametrize("white", [False, True])
 def test_composite_bwd_kernel_matches_autograd(white):
-    """nerfart_volsdf_composite_bwd against autograd through the reference formulas (autodiff.volsdf_composite)."""
+    """nerfart_volsdf_composite_bwd against autograd through the reference formulas (autodiff.volsdf_composite).  (fp64 bounds: tests/test_gpu_composite.py.)"""
     from nerfart_amd import autodiff, hip
     g = torch.Generator().manual_seed(5)
     R, P = 257, 192
