@@ -396,9 +396,30 @@ int nerfart_sphere_trace_step(const float* sdf, int n_rays, const float* far, fl
  *          H W / 16 a multiple of 64 (224 x 224 in the reference).
  * nerfart_vgg16_l1_fwd writes loss_out[0] (device) = mean |relu3_3(pred) - relu3_3(target)|; with keep_for_bwd the workspace
  * (nerfart_vgg16_workspace_bytes) keeps the activations and nerfart_vgg16_l1_bwd turns upstream[0] (device scalar, NULL = 1)
- * into g_img [1, 3, H, W] = d loss / d img2[0]. */
+ * into g_img [1, 3, H, W] = d loss / d img2[0].
+ *
+ * nerfart_vgg16_workspace_layout returns the same total as nerfart_vgg16_workspace_bytes (0 for H < 8 or W < 8) and, with offsets != NULL,
+ * fills offsets[15] with the byte offsets (256-byte aligned) of the workspace's buffers, in this order.  Every activation is NHWC fp32 and
+ * holds BOTH images, the prediction's rows first (image b, pixel (y, x), channel c at ((b h + y) w + x) C + c); h = H / 2^level, w = W / 2^level:
+ *    0  loss    64 floats: [0] the loss the forward accumulates, [8] the backward's scale = upstream / n, n = (H / 4)(W / 4) 256
+ *    1  cols    [2 H W, 32]    im2col of img2: column c 9 + ky 3 + kx < 27 = img2[b, c, y + ky - 1, x + kx - 1] (0 outside), columns 27..31 = 0
+ *    2  y[0]    [2, H, W, 64]            relu(conv1_1)        3  y[1]  [2, H, W, 64]           relu(conv1_2)
+ *    4  y[2]    [2, H/2, W/2, 128]       relu(conv2_1)        5  y[3]  [2, H/2, W/2, 128]      relu(conv2_2)
+ *    6  y[4]    [2, H/4, W/4, 256]       relu(conv3_1)        7  y[5]  [2, H/4, W/4, 256]      relu(conv3_2)
+ *    8  y[6]    [2, H/4, W/4, 256]       relu(conv3_3): the features the L1 is taken over
+ *    9  p[0]    [2, H/2, W/2, 64]        2 x 2 max-pool of y[1]       10  p[1]  [2, H/4, W/4, 128]   2 x 2 max-pool of y[3]
+ *   11  ga      keep_for_bwd only (else empty, as gb and dcols); after the forward [H/4, W/4, 256] = sign(fp - ft) [fp > 0] of y[6]
+ *               (prediction only; sign(0) = 0).  ga and gb are the backward's ping-pong cotangent buffers, H W x 64 floats each: the backward
+ *               OVERWRITES ga (run the forward again before a second backward) and leaves in it [H W, 64] = the cotangent of y[0], masked
+ *   12  gb      after the backward [H, W, 64] = the un-pooled cotangent of y[1], masked by y[1] > 0 (what conv1_2's backward read)
+ *   13  dcols   [H W, 64]  after the backward: column k = c 9 + ky 3 + kx < 27 = d loss n / d cols[pixel, k] of the prediction (before the
+ *               scale), columns 27..63 = 0; g_img[c, y, x] = scale * sum of the nine dcols entries whose window tap reads pixel (y, x)
+ *   14  total
+ * The backward decides from the stored fp32 activations: ReLU mask y > 0; un-pool to the first maximum of the 2 x 2 window in row-major
+ * scan (strict >), and only if that maximum is > 0. */
 long long nerfart_vgg16_blob_layout(long long* offsets);
 long long nerfart_vgg16_workspace_bytes(int H, int W, int keep_for_bwd);
+long long nerfart_vgg16_workspace_layout(int H, int W, int keep_for_bwd, long long* offsets);
 int nerfart_vgg16_l1_fwd(const void* blob, long long blob_bytes, const float* img2, int H, int W, float* loss_out, int keep_for_bwd, void* workspace,
                          long long workspace_bytes, void* stream);
 int nerfart_vgg16_l1_bwd(const void* blob, long long blob_bytes, int H, int W, const float* upstream, float* g_img, void* workspace, long long workspace_bytes, void* stream);

@@ -217,6 +217,24 @@ int nerfart_vgg16_pack(const float* const* weight, const float* const* bias, voi
     return 0;
 }
 long long nerfart_vgg16_workspace_bytes(int H, int W, int keep_for_bwd) { return (H >= 8 && W >= 8) ? work_layout(H, W, keep_for_bwd).total : 0; }
+// The byte offsets of that workspace's buffers (what the stage tests read): offsets[15] = loss, cols, y[0..6], p[0], p[1], ga, gb, dcols, total.
+long long nerfart_vgg16_workspace_layout(int H, int W, int keep_for_bwd, long long* offsets) {
+    if (H < 8 || W < 8) return 0;
+    const Work w = work_layout(H, W, keep_for_bwd);
+    if (offsets) {
+        int i = 0;
+        offsets[i++] = w.o_loss;
+        offsets[i++] = w.o_cols;
+        for (int l = 0; l < NCONV; ++l) offsets[i++] = w.o_y[l];
+        offsets[i++] = w.o_p[0];
+        offsets[i++] = w.o_p[1];
+        offsets[i++] = w.o_ga;
+        offsets[i++] = w.o_gb;
+        offsets[i++] = w.o_dcols;
+        offsets[i++] = w.total;
+    }
+    return w.total;
+}
 
 // img2 [2, 3, H, W] fp32: the normalised (and resized) prediction, then the target.  loss_out[0] = mean |relu3_3(pred) - relu3_3(target)|.
 int nerfart_vgg16_l1_fwd(const void* blob, long long blob_bytes, const float* img2, int H, int W, float* loss_out, int keep_for_bwd, void* workspace,

@@ -102,6 +102,7 @@ _SIGS = {
     "nerfart_gemm_f16_nn": (_i, [_p, _p, _i, _i, _i, _p, _p]),
     "nerfart_vgg16_blob_layout": (_ll, [_p]),
     "nerfart_vgg16_workspace_bytes": (_ll, [_i, _i, _i]),
+    "nerfart_vgg16_workspace_layout": (_ll, [_i, _i, _i, _p]),
     "nerfart_vgg16_l1_fwd": (_i, [_p, _ll, _p, _i, _i, _p, _i, _p, _ll, _p]),
     "nerfart_vgg16_l1_bwd": (_i, [_p, _ll, _i, _i, _p, _p, _p, _ll, _p]),
     "nerfart_first_crossing": (_i, [_p, _p, _i, _i, _f, _p, _p, _p, _p, _p, _p]),

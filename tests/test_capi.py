@@ -86,6 +86,15 @@ def test_new_entry_points_validate_their_arguments_without_a_gpu():
     offs = (C.c_longlong * 22)()
     total = lib.nerfart_vgg16_blob_layout(C.cast(offs, C.c_void_p))
     assert offs[21] == total and total > 2 * 2 * (64 * 64 + 9 * (64 * 64 + 64 * 128 + 128 * 128 + 128 * 256 + 2 * 256 * 256))
+    # the workspace's buffers (host arithmetic only): loss, cols, y[0..6], p[0], p[1], ga, gb, dcols, total - the total is _workspace_bytes'
+    wo = (C.c_longlong * 15)()
+    for keep in (0, 1):
+        wtotal = lib.nerfart_vgg16_workspace_layout(32, 64, keep, C.cast(wo, C.c_void_p))
+        assert wtotal == wo[14] == lib.nerfart_vgg16_workspace_bytes(32, 64, keep) == lib.nerfart_vgg16_workspace_layout(32, 64, keep, null)
+        assert list(wo) == sorted(wo) and wo[0] == 0 and wo[1] == 256 and wo[2] - wo[1] == 4 * 2 * 32 * 64 * 32 and wo[3] - wo[2] == 4 * 2 * 32 * 64 * 64
+        assert wo[10] - wo[9] == 4 * 2 * 16 * 32 * 64 and wo[11] - wo[10] == 4 * 2 * 8 * 16 * 128
+        assert (wo[12] - wo[11] == wo[13] - wo[12] == wo[14] - wo[13] == 4 * 32 * 64 * 64) if keep else (wo[11] == wo[14])
+    assert lib.nerfart_vgg16_workspace_layout(4, 64, 1, null) == 0
 
 
 def test_ctypes_signatures_have_the_headers_argument_counts_and_kinds():
