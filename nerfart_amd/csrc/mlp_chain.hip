@@ -657,18 +657,49 @@ static int check_nabla_ws(int precision, const void* ws, long long ws_bytes) {
 }
 }  // namespace nerfart
 
+// ---- the point queries: each entry point exists for explicit points and for rays + depths.  Either builds its PointSrc; what follows is shared ----
+static int sdf_query(const float* blob, int precision, const char* who, const PointSrc& s, float R_bg, float* sdf_out, int out_stride, hipStream_t st) {
+    if (int rc = validate_src(s)) return rc;
+    if (int rc = check_precision(precision, false, blob, who, true)) return rc;
+    if (precision == 5) return sdf_f16x1(blob, s, R_bg, sdf_out, out_stride, st);
+    if (precision == 4) return sdf_f16x2(blob, s, R_bg, sdf_out, out_stride, st);
+    if (precision == 1) return sdf_bf16(blob, s, R_bg, sdf_out, out_stride, st);
+    const long long M = s.M;
+    return launch_chain(0, M, k_sdf_only, (unsigned)((M + 127) / 128), st, blob, s, R_bg, sdf_out, out_stride);
+}
+
+static int sdf_nabla_query(const float* blob, int precision, const char* who, const PointSrc& s, float R_bg, float* sdf_out, float* nabla_out,
+                           float* h7_out, void* workspace, long long workspace_bytes, hipStream_t st) {
+    if (int rc = validate_src(s)) return rc;
+    if (int rc = check_precision(precision, true, blob, who)) return rc;
+    if (int rc = check_nabla_ws(precision, workspace, workspace_bytes)) return rc;
+    if (precision == 1 || precision == 2 || precision == 4) return sdf_nabla_bf16_dispatch(precision, blob, s, R_bg, sdf_out, nabla_out, h7_out, workspace, st);
+    return sdf_nabla_f32_dispatch(precision, blob, s, R_bg, sdf_out, nabla_out, h7_out, workspace, st);
+}
+
+static int radiance_query(const float* blob, int precision, const char* who, int view_tiles, const PointSrc& s, const float* nabla, const float* h7,
+                          float* rgb_out, hipStream_t st) {
+    if (int rc = validate_src(s)) return rc;
+    if (int rc = check_precision(precision, false, blob, who)) return rc;
+    if (precision == 4) return radiance_f16x2(blob, view_tiles, s, nabla, h7, rgb_out, st);
+    if (precision == 1) return radiance_bf16(blob, view_tiles, s, nabla, h7, rgb_out, st);
+    const long long M = s.M;
+    const unsigned nt = (unsigned)((M + 127) / 128);
+    if (view_tiles == 1) return launch_chain(2, M, k_radiance<1>, nt, st, blob, s, nabla, h7, rgb_out);
+    if (view_tiles == 3) return launch_chain(2, M, k_radiance<3>, nt, st, blob, s, nabla, h7, rgb_out);
+    set_last_error("radiance_fwd: view_tiles must be 1 (raw view dirs) or 3 (multires_view = 4)");
+    return 2;
+}
+
 extern "C" {
 
 int nerfart_sdf_fwd(const float* blob, int precision, const float* pts, long long M, float R_bg, float* sdf_out, void* stream) {
+    // refuses a bad precision before a bad M (its _rays twin looks at M first); sdf_query's own check then passes
     if (int rc = check_precision(precision, false, blob, "nerfart_sdf_fwd", true)) return rc;
     if (int rc = check_M(M)) return rc;
     if (M == 0) return 0;
-    PointSrc s = make_src(pts, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 0, M);
-    if (int rc = validate_src(s)) return rc;
-    if (precision == 5) return sdf_f16x1(blob, s, R_bg, sdf_out, 0, (hipStream_t)stream);
-    if (precision == 4) return sdf_f16x2(blob, s, R_bg, sdf_out, 0, (hipStream_t)stream);
-    if (precision == 1) return sdf_bf16(blob, s, R_bg, sdf_out, 0, (hipStream_t)stream);
-    return launch_chain(0, M, k_sdf_only, (unsigned)((M + 127) / 128), (hipStream_t)stream, blob, s, R_bg, sdf_out, 0);
+    return sdf_query(blob, precision, "nerfart_sdf_fwd", make_src(pts, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 0, M), R_bg, sdf_out, 0,
+                     (hipStream_t)stream);
 }
 
 int nerfart_sdf_fwd_rays(const float* blob, int precision, const float* rays_o, const float* rays_d, const int* ray_idx,
@@ -677,13 +708,8 @@ int nerfart_sdf_fwd_rays(const float* blob, int precision, const float* rays_o, 
     const long long M = (long long)n_slots * n_per_ray;
     if (int rc = check_M(M)) return rc;
     if (M == 0) return 0;
-    PointSrc s = make_src(nullptr, nullptr, rays_o, rays_d, ray_idx, depth, n_per_ray, depth_stride, M);
-    if (int rc = validate_src(s)) return rc;
-    if (int rc = check_precision(precision, false, blob, "nerfart_sdf_fwd_rays", true)) return rc;
-    if (precision == 5) return sdf_f16x1(blob, s, R_bg, sdf_out, out_stride, (hipStream_t)stream);
-    if (precision == 4) return sdf_f16x2(blob, s, R_bg, sdf_out, out_stride, (hipStream_t)stream);
-    if (precision == 1) return sdf_bf16(blob, s, R_bg, sdf_out, out_stride, (hipStream_t)stream);
-    return launch_chain(0, M, k_sdf_only, (unsigned)((M + 127) / 128), (hipStream_t)stream, blob, s, R_bg, sdf_out, out_stride);
+    return sdf_query(blob, precision, "nerfart_sdf_fwd_rays", make_src(nullptr, nullptr, rays_o, rays_d, ray_idx, depth, n_per_ray, depth_stride, M), R_bg,
+                     sdf_out, out_stride, (hipStream_t)stream);
 }
 
 long long nerfart_sdf_nabla_workspace_bytes(int precision) { return (long long)nabla_ws_bytes(precision); }
@@ -692,12 +718,8 @@ int nerfart_sdf_nabla_fwd(const float* blob, int precision, const float* pts, lo
                           float* nabla_out, float* h7_out, void* workspace, long long workspace_bytes, void* stream) {
     if (int rc = check_M(M)) return rc;
     if (M == 0) return 0;
-    PointSrc s = make_src(pts, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 0, M);
-    if (int rc = validate_src(s)) return rc;
-    if (int rc = check_precision(precision, true, blob, "nerfart_sdf_nabla_fwd")) return rc;
-    if (int rc = check_nabla_ws(precision, workspace, workspace_bytes)) return rc;
-    if (precision == 1 || precision == 2 || precision == 4) return sdf_nabla_bf16_dispatch(precision, blob, s, R_bg, sdf_out, nabla_out, h7_out, workspace, (hipStream_t)stream);
-    return sdf_nabla_f32_dispatch(precision, blob, s, R_bg, sdf_out, nabla_out, h7_out, workspace, (hipStream_t)stream);
+    return sdf_nabla_query(blob, precision, "nerfart_sdf_nabla_fwd", make_src(pts, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 0, M), R_bg, sdf_out,
+                           nabla_out, h7_out, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int nerfart_sdf_nabla_fwd_rays(const float* blob, int precision, const float* rays_o, const float* rays_d, const int* ray_idx,
@@ -706,12 +728,8 @@ int nerfart_sdf_nabla_fwd_rays(const float* blob, int precision, const float* ra
     const long long M = (long long)n_slots * n_per_ray;
     if (int rc = check_M(M)) return rc;
     if (M == 0) return 0;
-    PointSrc s = make_src(nullptr, nullptr, rays_o, rays_d, ray_idx, depth, n_per_ray, depth_stride, M);
-    if (int rc = validate_src(s)) return rc;
-    if (int rc = check_precision(precision, true, blob, "nerfart_sdf_nabla_fwd_rays")) return rc;
-    if (int rc = check_nabla_ws(precision, workspace, workspace_bytes)) return rc;
-    if (precision == 1 || precision == 2 || precision == 4) return sdf_nabla_bf16_dispatch(precision, blob, s, R_bg, sdf_out, nabla_out, h7_out, workspace, (hipStream_t)stream);
-    return sdf_nabla_f32_dispatch(precision, blob, s, R_bg, sdf_out, nabla_out, h7_out, workspace, (hipStream_t)stream);
+    return sdf_nabla_query(blob, precision, "nerfart_sdf_nabla_fwd_rays", make_src(nullptr, nullptr, rays_o, rays_d, ray_idx, depth, n_per_ray, depth_stride, M),
+                           R_bg, sdf_out, nabla_out, h7_out, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int nerfart_radiance_fwd(const float* blob, int precision, int view_tiles, const float* pts, const float* view, long long M,
@@ -719,16 +737,8 @@ int nerfart_radiance_fwd(const float* blob, int precision, int view_tiles, const
     if (int rc = check_M(M)) return rc;
     if (M == 0) return 0;
     if (!view) { set_last_error("radiance_fwd: view dirs required in pts mode"); return 2; }
-    PointSrc s = make_src(pts, view, nullptr, nullptr, nullptr, nullptr, 1, 0, M);
-    if (int rc = validate_src(s)) return rc;
-    if (int rc = check_precision(precision, false, blob, "nerfart_radiance_fwd")) return rc;
-    if (precision == 4) return radiance_f16x2(blob, view_tiles, s, nabla, h7, rgb_out, (hipStream_t)stream);
-    if (precision == 1) return radiance_bf16(blob, view_tiles, s, nabla, h7, rgb_out, (hipStream_t)stream);
-    const unsigned nt = (unsigned)((M + 127) / 128);
-    if (view_tiles == 1) return launch_chain(2, M, k_radiance<1>, nt, (hipStream_t)stream, blob, s, nabla, h7, rgb_out);
-    if (view_tiles == 3) return launch_chain(2, M, k_radiance<3>, nt, (hipStream_t)stream, blob, s, nabla, h7, rgb_out);
-    set_last_error("radiance_fwd: view_tiles must be 1 (raw view dirs) or 3 (multires_view = 4)");
-    return 2;
+    return radiance_query(blob, precision, "nerfart_radiance_fwd", view_tiles, make_src(pts, view, nullptr, nullptr, nullptr, nullptr, 1, 0, M), nabla, h7,
+                          rgb_out, (hipStream_t)stream);
 }
 
 int nerfart_radiance_fwd_rays(const float* blob, int precision, int view_tiles, const float* rays_o, const float* rays_d,
@@ -737,16 +747,8 @@ int nerfart_radiance_fwd_rays(const float* blob, int precision, int view_tiles, 
     const long long M = (long long)n_slots * n_per_ray;
     if (int rc = check_M(M)) return rc;
     if (M == 0) return 0;
-    PointSrc s = make_src(nullptr, nullptr, rays_o, rays_d, ray_idx, depth, n_per_ray, depth_stride, M);
-    if (int rc = validate_src(s)) return rc;
-    if (int rc = check_precision(precision, false, blob, "nerfart_radiance_fwd_rays")) return rc;
-    if (precision == 4) return radiance_f16x2(blob, view_tiles, s, nabla, h7, rgb_out, (hipStream_t)stream);
-    if (precision == 1) return radiance_bf16(blob, view_tiles, s, nabla, h7, rgb_out, (hipStream_t)stream);
-    const unsigned nt = (unsigned)((M + 127) / 128);
-    if (view_tiles == 1) return launch_chain(2, M, k_radiance<1>, nt, (hipStream_t)stream, blob, s, nabla, h7, rgb_out);
-    if (view_tiles == 3) return launch_chain(2, M, k_radiance<3>, nt, (hipStream_t)stream, blob, s, nabla, h7, rgb_out);
-    set_last_error("radiance_fwd: view_tiles must be 1 (raw view dirs) or 3 (multires_view = 4)");
-    return 2;
+    return radiance_query(blob, precision, "nerfart_radiance_fwd_rays", view_tiles,
+                          make_src(nullptr, nullptr, rays_o, rays_d, ray_idx, depth, n_per_ray, depth_stride, M), nabla, h7, rgb_out, (hipStream_t)stream);
 }
 
 

@@ -87,6 +87,10 @@ __device__ __forceinline__ float ray_point(float o, float d, float t) { return _
 }  // namespace nerfart
 
 // ---- host side -----------------------------------------------------------------------
+// The C ABI.  Every source in this directory includes this file, so every extern "C" definition, and every call from one source into another, is
+// compiled against the one public declaration: no source carries a prototype of its own.
+#include "../../include/nerfart_hip.h"
+
 namespace nerfart {
 void set_last_error(const char* s);
 int check_hip(hipError_t e, const char* what);

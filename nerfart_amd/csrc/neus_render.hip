@@ -5,7 +5,7 @@
 //
 // One 64-lane wave (= one workgroup) per ray, samples in LDS, as in volsdf_render.hip.
 #include "ray_common.h"
-#include <stdlib.h>
+#include "host_util.h"
 
 namespace nerfart {
 
@@ -168,28 +168,13 @@ k_composite_neus(int P, const float* __restrict__ d_all, const float* __restrict
     }
 }
 
-static inline size_t align_up_n(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace nerfart
 
 using namespace nerfart;
 
 extern "C" {
 
-int nerfart_sdf_fwd_rays(const float*, int, const float*, const float*, const int*, const float*, int, int, int, float, float*, int, void*);
-int nerfart_sdf_nabla_fwd_rays(const float*, int, const float*, const float*, const int*, const float*, int, int, int, float, float*, float*, float*, void*,
-                               long long, void*);
-long long nerfart_sdf_nabla_workspace_bytes(int precision);
-int nerfart_radiance_fwd_rays(const float*, int, int, const float*, const float*, const int*, const float*, int, int, int, const float*, const float*, float*, void*);
-int nerfart_normalize_dirs(const float*, float*, int, void*);
-int nerfart_linspace_depths(const float*, int, const float*, const float*, float, float, int, float*, int, void*);
-void nerfart_linspace(float, float, int, float*);
-
-static int set_lds_n(const void* k, size_t bytes) {
-    if (bytes > 160 * 1024) { set_last_error("per-ray kernel needs more than 160 KiB of LDS"); return 2; }
-    NERFART_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return 0;
-}
+static const char kLdsRefusal[] = "per-ray kernel needs more than 160 KiB of LDS";
 
 int nerfart_near_far_from_sphere(const float* rays_o, const float* rays_dn, int n_rays, float r, float* near,
                                  float* far, void* stream) {
@@ -208,7 +193,7 @@ static int upsample_step(bool direct, int n_rays, int n, int cap, int n_new, flo
     const int npad = n_new < 64 ? 64 : n_new;
     const size_t lds = ((size_t)4 * n + npad) * sizeof(float);
     const void* fn = direct ? (const void*)k_neus_upsample<true> : (const void*)k_neus_upsample<false>;
-    if (int rc = set_lds_n(fn, lds)) return rc;
+    if (int rc = set_lds(fn, lds, kLdsRefusal)) return rc;
     if (direct) hipLaunchKernelGGL(k_neus_upsample<true>, dim3(n_rays), dim3(64), lds, (hipStream_t)stream, n, cap, n_new, inv_s, d, sdf, u_new, u_new_stride, d_new);
     else hipLaunchKernelGGL(k_neus_upsample<false>, dim3(n_rays), dim3(64), lds, (hipStream_t)stream, n, cap, n_new, inv_s, d, sdf, u_new, u_new_stride, d_new);
     NERFART_HIP(hipGetLastError());
@@ -230,7 +215,7 @@ int nerfart_merge_sorted_pairs(int n_rays, int n, int cap, int n_new, float* d, 
     if (n_rays <= 0) return 0;
     if (n + n_new > cap) { set_last_error("merge_sorted_pairs: n + n_new exceeds the row capacity"); return 2; }
     const size_t lds = ((size_t)2 * n + 2 * n_new) * sizeof(float);
-    if (int rc = set_lds_n((const void*)k_merge_pairs, lds)) return rc;
+    if (int rc = set_lds((const void*)k_merge_pairs, lds, kLdsRefusal)) return rc;
     hipLaunchKernelGGL(k_merge_pairs, dim3(n_rays), dim3(64), lds, (hipStream_t)stream, n, cap, n_new, d, sdf, d_new, s_new);
     NERFART_HIP(hipGetLastError());
     return 0;
@@ -256,46 +241,45 @@ typedef struct {
     size_t nabla_ws_bytes;
 } neus_ws_t;
 
-static size_t carve_neus(char* base, int R, int n_samples, int n_imp, int k3_rays, neus_ws_t* w, int n_more = 0) {
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o += align_up_n(bytes); return base ? base + r : (char*)nullptr; };
+static neus_ws_t carve_neus(Carver& c, int R, int n_samples, int n_imp, int k3_rays, int n_more) {
+    neus_ws_t w;
     const int P = n_samples + n_imp;
-    float* p;
-    p = (float*)take((size_t)R * 12); if (w) w->rays_dn = p;
-    p = (float*)take((size_t)R * 4); if (w) w->near = p;
-    p = (float*)take((size_t)R * 4); if (w) w->far = p;
-    p = (float*)take((size_t)n_samples * 4); if (w) w->t_coarse = p;
-    p = (float*)take((size_t)(n_imp + 64) * 4); if (w) w->u_new = p;
-    p = (float*)take((size_t)R * P * 4); if (w) w->d = p;
-    p = (float*)take((size_t)R * P * 4); if (w) w->s = p;
-    p = (float*)take((size_t)R * n_imp * 4); if (w) w->d_new = p;
-    p = (float*)take((size_t)R * n_imp * 4); if (w) w->s_new = p;
-    p = (float*)take((size_t)R * (P - 1) * 4); if (w) w->d_mid = p;
-    p = (float*)take((size_t)R * P * 4); if (w) w->sdf = p;
-    p = (float*)take((size_t)R * P * 12); if (w) w->nabla = p;
+    w.rays_dn = c.take<float>((size_t)R * 3);
+    w.near = c.take<float>((size_t)R);
+    w.far = c.take<float>((size_t)R);
+    w.t_coarse = c.take<float>((size_t)n_samples);
+    w.u_new = c.take<float>((size_t)(n_imp + 64));
+    w.d = c.take<float>((size_t)R * P);
+    w.s = c.take<float>((size_t)R * P);
+    w.d_new = c.take<float>((size_t)R * n_imp);
+    w.s_new = c.take<float>((size_t)R * n_imp);
+    w.d_mid = c.take<float>((size_t)R * (P - 1));
+    w.sdf = c.take<float>((size_t)R * P);
+    w.nabla = c.take<float>((size_t)R * P * 3);
     const int rk = k3_rays < R ? k3_rays : R;
-    p = (float*)take((size_t)rk * (P - 1) * 12); if (w) w->nabla_mid = p;
-    p = (float*)take((size_t)rk * (P - 1) * 4); if (w) w->sdf_mid = p;
-    p = (float*)take((size_t)R * (P - 1) * 12); if (w) w->rad = p;
-    p = (float*)take((size_t)rk * (P - 1) * 256 * 4); if (w) w->h7 = p;
+    w.nabla_mid = c.take<float>((size_t)rk * (P - 1) * 3);
+    w.sdf_mid = c.take<float>((size_t)rk * (P - 1));
+    w.rad = c.take<float>((size_t)R * (P - 1) * 3);
+    w.h7 = c.take<float>((size_t)rk * (P - 1) * 256);
     const long long nb0 = nerfart_sdf_nabla_workspace_bytes(0), nb1 = nerfart_sdf_nabla_workspace_bytes(1);
-    const size_t nb = (size_t)(nb0 > nb1 ? nb0 : nb1);
-    char* np = take(nb);
-    if (w) { w->nabla_ws = np; w->nabla_ws_bytes = nb; }
+    w.nabla_ws_bytes = (size_t)(nb0 > nb1 ? nb0 : nb1);
+    w.nabla_ws = c.take<char>(w.nabla_ws_bytes);
     // (appended: the layout of everything above does not depend on the up-sampling algorithm)
-    p = (float*)take((size_t)n_more * 4); if (w) w->t_more = p;
-    p = (float*)take((size_t)R * n_more * 4); if (w) w->d_more = p;
-    p = (float*)take((size_t)R * n_more * 4); if (w) w->s_more = p;
-    return o;
-}
-
-long long nerfart_neus_render_workspace_bytes(int n_rays, int n_samples, int n_importance, int k3_rays_chunk) {
-    return (long long)carve_neus(nullptr, n_rays, n_samples, n_importance, k3_rays_chunk, nullptr);
+    w.t_more = c.take<float>((size_t)n_more);
+    w.d_more = c.take<float>((size_t)R * n_more);
+    w.s_more = c.take<float>((size_t)R * n_more);
+    return w;
 }
 
 long long nerfart_neus_render_algo_workspace_bytes(int n_rays, int n_samples, int n_importance, int k3_rays_chunk, int upsample_algo,
                                                    int n_nograd_samples) {
-    return (long long)carve_neus(nullptr, n_rays, n_samples, n_importance, k3_rays_chunk, nullptr, upsample_algo == 2 ? n_nograd_samples : 0);
+    Carver c(nullptr);
+    carve_neus(c, n_rays, n_samples, n_importance, k3_rays_chunk, upsample_algo == 2 ? n_nograd_samples : 0);
+    return (long long)c.off;
+}
+
+long long nerfart_neus_render_workspace_bytes(int n_rays, int n_samples, int n_importance, int k3_rays_chunk) {
+    return nerfart_neus_render_algo_workspace_bytes(n_rays, n_samples, n_importance, k3_rays_chunk, 0, 0);
 }
 
 // NeuS volume_render for one chunk of rays (N_outside = 0).  upsample_algo: 0 'official_solution' (neus.py:275-303: n_upsample_iters
@@ -333,24 +317,16 @@ int nerfart_neus_render_algo_fwd(const float* surf_blob, const float* rad_blob, 
     const int P = n_samples + n_importance, n_new = n_importance / n_upsample_iters;
     const int n_more = upsample_algo == 2 ? n_nograd_samples : 0;
     if (u_new_per_ray && !u_new_dev) { set_last_error("neus render: u_new_per_ray needs u_new_dev [n_rays, n_importance]"); return 2; }
-    neus_ws_t w;
-    const size_t need = carve_neus((char*)workspace, n_rays, n_samples, n_importance, k3_rays_chunk, &w, n_more);
-    if (!workspace || (size_t)workspace_bytes < need) { set_last_error("neus render: workspace too small"); return 2; }
+    Carver carver(workspace);
+    neus_ws_t w = carve_neus(carver, n_rays, n_samples, n_importance, k3_rays_chunk, n_more);
+    if (!workspace || (size_t)workspace_bytes < carver.off) { set_last_error("neus render: workspace too small"); return 2; }
     float* sdf = sdf_out ? sdf_out : w.sdf;
     float* nabla = nabla_out ? nabla_out : w.nabla;
     float* rad = radiance_out ? radiance_out : w.rad;
     if (t_coarse_dev && u_new_dev) {
         w.t_coarse = const_cast<float*>(t_coarse_dev); w.u_new = const_cast<float*>(u_new_dev);
     } else {
-        float* h = (float*)malloc(sizeof(float) * (size_t)(n_samples + n_new));
-        if (!h) { set_last_error("out of host memory"); return 3; }
-        nerfart_linspace(0.f, 1.f, n_samples, h);
-        nerfart_linspace(0.f, 1.f, n_new, h + n_samples);
-        hipError_t e1 = hipMemcpyAsync(w.t_coarse, h, sizeof(float) * n_samples, hipMemcpyHostToDevice, stream);
-        hipError_t e2 = hipMemcpyAsync(w.u_new, h + n_samples, sizeof(float) * n_new, hipMemcpyHostToDevice, stream);
-        hipError_t e3 = hipStreamSynchronize(stream);
-        free(h);
-        NERFART_HIP(e1); NERFART_HIP(e2); NERFART_HIP(e3);
+        if (int rc = upload_linspace_tables({{w.t_coarse, n_samples}, {w.u_new, n_new}}, stream)) return rc;
         if (u_new_per_ray) w.u_new = const_cast<float*>(u_new_dev);
     }
     if (int rc = nerfart_normalize_dirs(rays_d, w.rays_dn, n_rays, stream)) return rc;
@@ -372,14 +348,8 @@ int nerfart_neus_render_algo_fwd(const float* surf_blob, const float* rad_blob, 
         if (upsample_algo == 2) {                                 // neus.py:260-263: N_nograd_samples evenly spaced samples, sdf without gradient
             if (t_nograd_dev) {
                 w.t_more = const_cast<float*>(t_nograd_dev);
-            } else {
-                float* h = (float*)malloc(sizeof(float) * (size_t)n_more);
-                if (!h) { set_last_error("out of host memory"); return 3; }
-                nerfart_linspace(0.f, 1.f, n_more, h);
-                hipError_t e1 = hipMemcpyAsync(w.t_more, h, sizeof(float) * n_more, hipMemcpyHostToDevice, stream);
-                hipError_t e2 = hipStreamSynchronize(stream);
-                free(h);
-                NERFART_HIP(e1); NERFART_HIP(e2);
+            } else if (int rc = upload_linspace_tables({{w.t_more, n_more}}, stream)) {
+                return rc;
             }
             if (int rc = nerfart_linspace_depths(w.t_more, n_more, w.near, w.far, 0.f, 0.f, n_rays, w.d_more, n_more, stream)) return rc;
             if (int rc = nerfart_sdf_fwd_rays(surf_blob, precision, rays_o, w.rays_dn, nullptr, w.d_more, n_rays, n_more, n_more, 0.f, w.s_more, n_more, stream)) return rc;

@@ -23,8 +23,7 @@
 //   backward -> radiance backward (deltas, g_h7, g_n) -> cotangents of the second-order SDF sweep (sphere clamp mask, eikonal
 //   gradient with the per-patch mean) -> k_sdf_fwd2 / k_sdf_bwd2 -> the weight-gradient reductions over the point-major dumps.
 // Everything runs on the caller's stream out of ONE caller-owned workspace; nothing is allocated, nothing synchronises.
-#include "nerfart_common.h"
-#include "../../include/nerfart_hip.h"
+#include "host_util.h"
 #include <string>
 
 namespace nerfart {
@@ -224,13 +223,7 @@ __global__ void __launch_bounds__(64) k_weight_norm_bwd(const float* __restrict_
     }
 }
 
-// ---- workspace carving -----------------------------------------------------------------------------------------------------------
-struct Carver {
-    char* base; size_t off;
-    explicit Carver(void* p) : base((char*)p), off(0) {}
-    template <class T> T* take(size_t n) { T* r = base ? (T*)(base + off) : nullptr; off += (n * sizeof(T) + 255) & ~(size_t)255; return r; }
-    void* bytes(size_t n) { return take<char>(n); }
-};
+// ---- workspace carving (Carver: host_util.h) -------------------------------------------------------------------------------------
 static inline long long up(long long m, long long k) { return (m + k - 1) / k * k; }
 static inline long long max3(long long a, long long b, long long c) { return a > b ? (a > c ? a : c) : (b > c ? b : c); }
 

@@ -10,8 +10,7 @@
 //        | else: 10-step bisection for beta+ and re-queue).
 // One 4-byte device->host read of the active count per round is the only host synchronisation.
 #include "ray_common.h"
-#include <stdio.h>
-#include <stdlib.h>
+#include "host_util.h"
 
 namespace nerfart {
 
@@ -331,21 +330,11 @@ __global__ void k_scatter_samples(const int* __restrict__ list, int n, int n_fin
     if (t == 0) { beta_map[ray] = c_beta[slot]; iter_usage[ray] = c_iter[slot]; }
 }
 
-static inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-static inline int next_pow2(int x) { int p = 1; while (p < x) p <<= 1; return p; }
-
 }  // namespace nerfart
 
 using namespace nerfart;
 
 extern "C" {
-
-// ---- forward declarations of the MLP entry points (mlp_chain.hip) ---------------------
-int nerfart_sdf_fwd_rays(const float*, int, const float*, const float*, const int*, const float*, int, int, int, float, float*, int, void*);
-int nerfart_sdf_nabla_fwd_rays(const float*, int, const float*, const float*, const int*, const float*, int, int, int, float, float*, float*, float*, void*,
-                               long long, void*);
-long long nerfart_sdf_nabla_workspace_bytes(int precision);
-int nerfart_radiance_fwd_rays(const float*, int, int, const float*, const float*, const int*, const float*, int, int, int, const float*, const float*, float*, void*);
 
 // torch.linspace(start, end, n) in fp32: step = (end-start)/(n-1); the first half counts up from
 // start, the second half down from end (ATen RangeFactories linspace kernel).  Host helper.
@@ -386,11 +375,7 @@ static int check_rows(const char* who, int n, int cap, int n_extra) {
     return 2;
 }
 
-static int set_lds(const void* k, size_t bytes) {
-    if (bytes > 160 * 1024) { set_last_error("per-ray kernel needs more than 160 KiB of LDS (too many samples per ray)"); return 2; }
-    NERFART_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return 0;
-}
+static const char kLdsRefusal[] = "per-ray kernel needs more than 160 KiB of LDS (too many samples per ray)";
 
 // guard / esc_list / esc_count: see SamplerParams (the exported stage entry point runs with the guard off)
 static int first_check_launch(int n_rays, int n, int cap, int n_final, float eps, float alpha_net, float beta_net,
@@ -401,7 +386,7 @@ static int first_check_launch(int n_rays, int n, int cap, int n_final, float eps
     if (n_rays <= 0) return 0;
     SamplerParams P{n, cap, 0, n_final, 0, 0, eps, alpha_net, beta_net, u_final_stride, guard, esc_list, esc_count};
     const size_t lds = (size_t)3 * n * sizeof(float);
-    if (int rc = set_lds((const void*)k_first_check, lds)) return rc;
+    if (int rc = set_lds((const void*)k_first_check, lds, kLdsRefusal)) return rc;
     hipLaunchKernelGGL(k_first_check, dim3(n_rays), dim3(64), lds, (hipStream_t)stream, P, dA, sA, u_final,
                        beta_plus0_denom, far, far_s, d_fine, beta_plus, beta_map, iter_usage, act_out, act_count);
     NERFART_HIP(hipGetLastError());
@@ -424,7 +409,7 @@ static int upsample_launch(int n_active, int n, int cap, int n_up, const float* 
     if (n_up & (n_up - 1)) { set_last_error("n_up must be a power of two"); return 2; }
     SamplerParams P{n, cap, n_up, 0, 0, 0, 0.f, 0.f, 0.f};
     const size_t lds = ((size_t)4 * n + n_up) * sizeof(float);
-    if (int rc = set_lds((const void*)k_upsample, lds)) return rc;
+    if (int rc = set_lds((const void*)k_upsample, lds, kLdsRefusal)) return rc;
     hipLaunchKernelGGL(k_upsample, dim3(n_active), dim3(64), lds, (hipStream_t)stream, P, dA, sA, act, beta_plus, u_up,
                        clamp_bounds, d_new);
     NERFART_HIP(hipGetLastError());
@@ -446,7 +431,7 @@ static int merge_check_launch(int n_active, int n, int cap, int n_up, int n_fina
     if (n_active <= 0) return 0;
     SamplerParams P{n, cap, n_up, n_final, max_bisect, it, eps, alpha_net, beta_net, u_final_stride, guard, esc_list, esc_count};
     const size_t lds = ((size_t)3 * n + 3 * n_up) * sizeof(float);
-    if (int rc = set_lds((const void*)k_merge_check, lds)) return rc;
+    if (int rc = set_lds((const void*)k_merge_check, lds, kLdsRefusal)) return rc;
     hipLaunchKernelGGL(k_merge_check, dim3(n_active), dim3(64), lds, (hipStream_t)stream, P, dA, sA, dB, sB, act, d_new,
                        s_new, u_final, d_fine, beta_plus, beta_map, iter_usage, act_out, act_count);
     NERFART_HIP(hipGetLastError());
@@ -470,7 +455,7 @@ static int finalize_launch(int n_active, int n, int cap, int n_final, const floa
     if (n_active <= 0) return 0;
     SamplerParams P{n, cap, 0, n_final, 0, 0, 0.f, 0.f, 0.f, u_final_stride};
     const size_t lds = (size_t)3 * n * sizeof(float);
-    if (int rc = set_lds((const void*)k_finalize_unconverged, lds)) return rc;
+    if (int rc = set_lds((const void*)k_finalize_unconverged, lds, kLdsRefusal)) return rc;
     hipLaunchKernelGGL(k_finalize_unconverged, dim3(n_active), dim3(64), lds, (hipStream_t)stream, P, dA, sA, act,
                        u_final, beta_plus, d_fine, beta_map, iter_usage);
     NERFART_HIP(hipGetLastError());
@@ -490,7 +475,7 @@ int nerfart_sort_concat(int n_rays, const float* a, int na, int a_stride, const 
     if (n_rays <= 0) return 0;
     const int npad = next_pow2(na + nb);
     const size_t lds = (size_t)npad * sizeof(float);
-    if (int rc = set_lds((const void*)k_sort_concat, lds)) return rc;
+    if (int rc = set_lds((const void*)k_sort_concat, lds, kLdsRefusal)) return rc;
     hipLaunchKernelGGL(k_sort_concat, dim3(n_rays), dim3(64), lds, (hipStream_t)stream, a, na, a_stride, b, nb, b_stride,
                        npad, out, out_stride);
     NERFART_HIP(hipGetLastError());
@@ -522,39 +507,42 @@ typedef struct {
 
 enum { COUNT_SLOTS = 64, ESC_SLOT = COUNT_SLOTS - 1 };     // w.count: one active-ray counter per round + the escalation list's length
 
-static size_t carve_sampler(char* base, int R, int cap, int n_up, int n0, int n_final, sampler_ws_t* w) {
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o += align_up(bytes); return base ? base + r : (char*)nullptr; };
-    const size_t row = (size_t)R * cap * sizeof(float);
-    float* p;
-    p = (float*)take(row); if (w) w->dA = p;
-    p = (float*)take(row); if (w) w->sA = p;
-    p = (float*)take(row); if (w) w->dB = p;
-    p = (float*)take(row); if (w) w->sB = p;
-    p = (float*)take((size_t)R * n_up * sizeof(float)); if (w) w->d_new = p;
-    p = (float*)take((size_t)R * n_up * sizeof(float)); if (w) w->s_new = p;
-    p = (float*)take((size_t)R * sizeof(float)); if (w) w->beta_plus = p;
-    int* q;
-    q = (int*)take((size_t)R * sizeof(int)); if (w) w->act0 = q;
-    q = (int*)take((size_t)R * sizeof(int)); if (w) w->act1 = q;
-    q = (int*)take(COUNT_SLOTS * sizeof(int)); if (w) w->count = q;
-    p = (float*)take((size_t)n0 * sizeof(float)); if (w) w->t_init = p;
-    p = (float*)take((size_t)(n_up + 2) * sizeof(float)); if (w) w->u_up = p;
-    p = (float*)take((size_t)n_final * sizeof(float)); if (w) w->u_final = p;
-    q = (int*)take((size_t)R * sizeof(int)); if (w) w->esc_list = q;
-    p = (float*)take((size_t)R * 3 * sizeof(float)); if (w) w->c_o = p;
-    p = (float*)take((size_t)R * 3 * sizeof(float)); if (w) w->c_dn = p;
-    p = (float*)take((size_t)R * sizeof(float)); if (w) w->c_near = p;
-    p = (float*)take((size_t)R * sizeof(float)); if (w) w->c_far = p;
-    p = (float*)take((size_t)R * n_final * sizeof(float)); if (w) w->c_u = p;
-    p = (float*)take((size_t)R * n_final * sizeof(float)); if (w) w->c_d_fine = p;
-    p = (float*)take((size_t)R * sizeof(float)); if (w) w->c_beta = p;
-    p = (float*)take((size_t)R * sizeof(float)); if (w) w->c_iter = p;
-    return o;
+static sampler_ws_t carve_sampler(Carver& c, int R, int cap, int n_up, int n0, int n_final) {
+    sampler_ws_t w;
+    const size_t row = (size_t)R * cap;
+    w.dA = c.take<float>(row);
+    w.sA = c.take<float>(row);
+    w.dB = c.take<float>(row);
+    w.sB = c.take<float>(row);
+    w.d_new = c.take<float>((size_t)R * n_up);
+    w.s_new = c.take<float>((size_t)R * n_up);
+    w.beta_plus = c.take<float>((size_t)R);
+    w.act0 = c.take<int>((size_t)R);
+    w.act1 = c.take<int>((size_t)R);
+    w.count = c.take<int>(COUNT_SLOTS);
+    w.t_init = c.take<float>((size_t)n0);
+    w.u_up = c.take<float>((size_t)(n_up + 2));
+    w.u_final = c.take<float>((size_t)n_final);
+    w.esc_list = c.take<int>((size_t)R);
+    w.c_o = c.take<float>((size_t)R * 3);
+    w.c_dn = c.take<float>((size_t)R * 3);
+    w.c_near = c.take<float>((size_t)R);
+    w.c_far = c.take<float>((size_t)R);
+    w.c_u = c.take<float>((size_t)R * n_final);
+    w.c_d_fine = c.take<float>((size_t)R * n_final);
+    w.c_beta = c.take<float>((size_t)R);
+    w.c_iter = c.take<float>((size_t)R);
+    return w;
+}
+
+static size_t sampler_bytes(int R, int cap, int n_up, int n0, int n_final) {
+    Carver c(nullptr);
+    carve_sampler(c, R, cap, n_up, n0, n_final);
+    return c.off;
 }
 
 long long nerfart_volsdf_sampler_workspace_bytes(int n_rays, int n_init, int n_up, int n_final, int max_iter) {
-    return (long long)carve_sampler(nullptr, n_rays, n_init + max_iter * n_up, n_up, n_init, n_final, nullptr);
+    return (long long)sampler_bytes(n_rays, n_init + max_iter * n_up, n_up, n_init, n_final);
 }
 
 // fine_sample (volsdf.py:97-302) for n_rays rays with already normalised directions.
@@ -583,9 +571,9 @@ static int fine_sample_run(const float* surf_blob, int precision, const float* e
     if (!guarded) guard = 0.f;
     const int u_stride = u_final_per_ray ? n_final : 0;
     const int cap = n_init + max_iter * n_up;
-    sampler_ws_t w;
-    const size_t need = carve_sampler((char*)workspace, n_rays, cap, n_up, n_init, n_final, &w);
-    if (!workspace || (size_t)workspace_bytes < need) { set_last_error("fine_sample: workspace too small"); return 2; }
+    Carver carver(workspace);
+    sampler_ws_t w = carve_sampler(carver, n_rays, cap, n_up, n_init, n_final);
+    if (!workspace || (size_t)workspace_bytes < carver.off) { set_last_error("fine_sample: workspace too small"); return 2; }
     // linspace tables: torch.linspace(0, 1, n) for n = n_init, n_up + 2, n_final.  Callers that hold the
     // host framework's own tables pass them (torch's CPU kernel is vectorised and differs from the scalar
     // formula by an ulp on some entries); otherwise the library's nerfart_linspace is used.
@@ -593,17 +581,7 @@ static int fine_sample_run(const float* surf_blob, int precision, const float* e
     if (!own_tables) {
         w.t_init = const_cast<float*>(t_init_dev); w.u_up = const_cast<float*>(u_up_dev); w.u_final = const_cast<float*>(u_final_dev);
     } else {
-        float* h = (float*)malloc(sizeof(float) * (size_t)(n_init + n_up + 2 + n_final));
-        if (!h) { set_last_error("out of host memory"); return 3; }
-        nerfart_linspace(0.f, 1.f, n_init, h);
-        nerfart_linspace(0.f, 1.f, n_up + 2, h + n_init);
-        nerfart_linspace(0.f, 1.f, n_final, h + n_init + n_up + 2);
-        hipError_t e1 = hipMemcpyAsync(w.t_init, h, sizeof(float) * n_init, hipMemcpyHostToDevice, stream);
-        hipError_t e2 = hipMemcpyAsync(w.u_up, h + n_init, sizeof(float) * (n_up + 2), hipMemcpyHostToDevice, stream);
-        hipError_t e3 = hipMemcpyAsync(w.u_final, h + n_init + n_up + 2, sizeof(float) * n_final, hipMemcpyHostToDevice, stream);
-        hipError_t e4 = hipStreamSynchronize(stream);
-        free(h);
-        NERFART_HIP(e1); NERFART_HIP(e2); NERFART_HIP(e3); NERFART_HIP(e4);
+        if (int rc = upload_linspace_tables({{w.t_init, n_init}, {w.u_up, n_up + 2}, {w.u_final, n_final}}, stream)) return rc;
         if (u_final_per_ray) w.u_final = const_cast<float*>(u_final_dev);
     }
     if (int rc = nerfart_linspace_depths(w.t_init, n_init, near, far, near_s, far_s, n_rays, w.dA, cap, stream)) return rc;
@@ -716,37 +694,35 @@ typedef struct {
     size_t nabla_ws_bytes;
 } render_ws_t;
 
-static size_t carve_render(char* base, int R, int n_samples, int n_imp, int max_iter, int k3_rays, render_ws_t* w) {
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o += align_up(bytes); return base ? base + r : (char*)nullptr; };
+static render_ws_t carve_render(Carver& c, int R, int n_samples, int n_imp, int max_iter, int k3_rays) {
+    render_ws_t w;
     const int P = n_samples + n_imp;
     const int n_init = 4 * n_samples, n_up = 4 * n_samples;
-    float* p;
-    p = (float*)take((size_t)R * 3 * 4); if (w) w->rays_dn = p;
-    p = (float*)take((size_t)R * n_imp * 4); if (w) w->d_fine = p;
-    p = (float*)take((size_t)R * n_samples * 4); if (w) w->d_coarse = p;
-    p = (float*)take((size_t)n_samples * 4); if (w) w->t_coarse = p;
-    p = (float*)take((size_t)R * P * 4); if (w) w->d_all = p;
-    p = (float*)take((size_t)R * P * 4); if (w) w->sdf = p;
-    p = (float*)take((size_t)R * P * 12); if (w) w->nabla = p;
-    p = (float*)take((size_t)R * P * 12); if (w) w->rad = p;
-    p = (float*)take((size_t)R * 4); if (w) w->beta_map = p;
-    p = (float*)take((size_t)R * 4); if (w) w->iter_usage = p;
+    w.rays_dn = c.take<float>((size_t)R * 3);
+    w.d_fine = c.take<float>((size_t)R * n_imp);
+    w.d_coarse = c.take<float>((size_t)R * n_samples);
+    w.t_coarse = c.take<float>((size_t)n_samples);
+    w.d_all = c.take<float>((size_t)R * P);
+    w.sdf = c.take<float>((size_t)R * P);
+    w.nabla = c.take<float>((size_t)R * P * 3);
+    w.rad = c.take<float>((size_t)R * P * 3);
+    w.beta_map = c.take<float>((size_t)R);
+    w.iter_usage = c.take<float>((size_t)R);
     const int rk = k3_rays < R ? k3_rays : R;
-    p = (float*)take((size_t)rk * P * 256 * 4); if (w) w->h7 = p;
-    const size_t sb = carve_sampler(nullptr, R, n_init + max_iter * n_up, n_up, n_init, n_imp, nullptr);
-    char* sp = take(sb);
-    if (w) { w->sampler = sp; w->sampler_bytes = sb; }
+    w.h7 = c.take<float>((size_t)rk * P * 256);
+    w.sampler_bytes = sampler_bytes(R, n_init + max_iter * n_up, n_up, n_init, n_imp);
+    w.sampler = c.take<char>(w.sampler_bytes);
     const long long nb0 = nerfart_sdf_nabla_workspace_bytes(0), nb1 = nerfart_sdf_nabla_workspace_bytes(1);
-    const size_t nb = (size_t)(nb0 > nb1 ? nb0 : nb1);          // sized for either precision
-    char* np = take(nb);
-    if (w) { w->nabla_ws = np; w->nabla_ws_bytes = nb; }
-    return o;
+    w.nabla_ws_bytes = (size_t)(nb0 > nb1 ? nb0 : nb1);         // sized for either precision
+    w.nabla_ws = c.take<char>(w.nabla_ws_bytes);
+    return w;
 }
 
 long long nerfart_volsdf_render_workspace_bytes(int n_rays, int n_samples, int n_importance, int max_upsample_steps,
                                                 int k3_rays_chunk) {
-    return (long long)carve_render(nullptr, n_rays, n_samples, n_importance, max_upsample_steps, k3_rays_chunk, nullptr);
+    Carver c(nullptr);
+    carve_render(c, n_rays, n_samples, n_importance, max_upsample_steps, k3_rays_chunk);
+    return (long long)c.off;
 }
 
 // Renders n_rays rays (rays_d un-normalised, as get_rays returns them).  Outputs rgb [R,3], depth [R],
@@ -772,9 +748,9 @@ int nerfart_volsdf_render_staged2_fwd(const float* surf_blob, int precision, con
     if (!sampler_blob) { set_last_error("render: sampler_blob is NULL"); return 2; }
     if (n_samples < 2 || n_importance < 1 || k3_rays_chunk < 1) { set_last_error("render: bad sample counts"); return 2; }
     const int P = n_samples + n_importance;
-    render_ws_t w;
-    const size_t need = carve_render((char*)workspace, n_rays, n_samples, n_importance, max_upsample_steps, k3_rays_chunk, &w);
-    if (!workspace || (size_t)workspace_bytes < need) { set_last_error("render: workspace too small"); return 2; }
+    Carver carver(workspace);
+    render_ws_t w = carve_render(carver, n_rays, n_samples, n_importance, max_upsample_steps, k3_rays_chunk);
+    if (!workspace || (size_t)workspace_bytes < carver.off) { set_last_error("render: workspace too small"); return 2; }
     float* d_all = d_all_out ? d_all_out : w.d_all;
     float* sdf = sdf_out ? sdf_out : w.sdf;
     float* nabla = nabla_out ? nabla_out : w.nabla;
@@ -790,14 +766,8 @@ int nerfart_volsdf_render_staged2_fwd(const float* surf_blob, int precision, con
                                  u_final_per_ray, w.d_fine, beta_map, iter_usage, w.sampler, (long long)w.sampler_bytes, n_escalated, stream)) return rc;
     if (t_coarse_dev) {
         w.t_coarse = const_cast<float*>(t_coarse_dev);
-    } else {
-        float* h = (float*)malloc(sizeof(float) * (size_t)n_samples);
-        if (!h) { set_last_error("out of host memory"); return 3; }
-        nerfart_linspace(0.f, 1.f, n_samples, h);
-        hipError_t e1 = hipMemcpyAsync(w.t_coarse, h, sizeof(float) * n_samples, hipMemcpyHostToDevice, stream);
-        hipError_t e2 = hipStreamSynchronize(stream);
-        free(h);
-        NERFART_HIP(e1); NERFART_HIP(e2);
+    } else if (int rc = upload_linspace_tables({{w.t_coarse, n_samples}}, stream)) {
+        return rc;
     }
     if (int rc = nerfart_linspace_depths(w.t_coarse, n_samples, nullptr, nullptr, near_s, far_s, n_rays, w.d_coarse, n_samples, stream)) return rc;
     if (int rc = nerfart_sort_concat(n_rays, w.d_coarse, n_samples, n_samples, w.d_fine, n_importance, n_importance, d_all, P, stream)) return rc;

@@ -221,6 +221,51 @@ def test_stage_entry_points_refuse_rows_that_do_not_fit_their_stride():
         assert step(1, 1, 64, 16, 64.0, null, null, null, 0, null, null) == 2 and "n >= 2" in err()
 
 
+def test_render_workspace_sizes_are_the_sums_of_their_documented_buffers():
+    """The forward renderers' workspaces are caller-allocated and carved in a fixed order, every buffer rounded up to 256 bytes (and the
+    sampler's escalation run relies on its buffers sitting behind everything a smaller run carves): the four byte-count queries against the
+    layouts written out here, buffer by buffer in carving order.  Host arithmetic only."""
+    from nerfart_amd import hip
+    lib = hip.lib
+    total = lambda sizes: sum((b + 255) // 256 * 256 for b in sizes)
+    nabla_ws = 256 << 20        # grad(SDF) scratch, sized for either precision: the fp32 kernel's 1 MiB per CU, 256 CUs (also the count assumed without a GPU)
+
+    def sampler(R, n_init, n_up, n_final, max_iter):
+        cap = n_init + max_iter * n_up
+        return total([4 * R * cap] * 4                              # dA, sA, dB, sB
+                     + [4 * R * n_up] * 2 + [4 * R]                 # d_new, s_new, beta_plus
+                     + [4 * R] * 2 + [4 * 64]                       # act0, act1, count (64 counters)
+                     + [4 * n_init, 4 * (n_up + 2), 4 * n_final]    # t_init, u_up, u_final
+                     + [4 * R]                                      # esc_list; then the compacted rays of the escalation run and its outputs:
+                     + [12 * R] * 2 + [4 * R] * 2                   # c_o, c_dn, c_near, c_far
+                     + [4 * R * n_final] * 2 + [4 * R] * 2)         # c_u, c_d_fine, c_beta, c_iter
+
+    def volsdf(R, ns, ni, max_iter, k3):
+        P, rk = ns + ni, min(k3, R)
+        return total([12 * R, 4 * R * ni, 4 * R * ns, 4 * ns]       # rays_dn, d_fine, d_coarse, t_coarse
+                     + [4 * R * P] * 2 + [12 * R * P] * 2           # d_all, sdf, nabla, rad
+                     + [4 * R] * 2                                  # beta_map, iter_usage
+                     + [4 * rk * P * 256]                           # h7 of one radiance chunk
+                     + [sampler(R, 4 * ns, 4 * ns, ni, max_iter), nabla_ws])
+
+    def neus(R, ns, ni, k3, n_more):
+        P, rk = ns + ni, min(k3, R)
+        return total([12 * R, 4 * R, 4 * R, 4 * ns, 4 * (ni + 64)]  # rays_dn, near, far, t_coarse, u_new
+                     + [4 * R * P] * 2 + [4 * R * ni] * 2           # d, s, d_new, s_new
+                     + [4 * R * (P - 1), 4 * R * P, 12 * R * P]     # d_mid, sdf, nabla
+                     + [12 * rk * (P - 1), 4 * rk * (P - 1)]        # nabla_mid, sdf_mid of one radiance chunk
+                     + [12 * R * (P - 1), 4 * rk * (P - 1) * 256]   # rad, h7
+                     + [nabla_ws]
+                     + [4 * n_more] + [4 * R * n_more] * 2)         # 'direct_more' only: t_more, d_more, s_more
+
+    for R, ns, ni, max_iter, k3 in ((1, 2, 1, 0, 1), (3, 8, 5, 2, 2), (1200, 128, 64, 5, 512)):
+        assert lib.nerfart_volsdf_sampler_workspace_bytes(R, 4 * ns, 4 * ns, ni, max_iter) == sampler(R, 4 * ns, 4 * ns, ni, max_iter)
+        assert lib.nerfart_volsdf_render_workspace_bytes(R, ns, ni, max_iter, k3) == volsdf(R, ns, ni, max_iter, k3)
+        assert lib.nerfart_neus_render_workspace_bytes(R, ns, ni, k3) == neus(R, ns, ni, k3, 0)
+        for n_nograd in (2, 2048):
+            assert lib.nerfart_neus_render_algo_workspace_bytes(R, ns, ni, k3, 2, n_nograd) == neus(R, ns, ni, k3, n_nograd)
+
+
 def test_composite_entry_points_refuse_rows_without_an_interval():
     """nerfart_volsdf_composite / nerfart_neus_composite integrate P - 1 intervals: P < 2 is refused with a message after the empty-launch return and
     before any HIP call (with P <= 0 and the detail outputs set, lane 0 would read and write outside the row) - here with null buffers.  The two
