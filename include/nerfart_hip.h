@@ -43,6 +43,8 @@
 #ifndef NERFART_HIP_H
 #define NERFART_HIP_H
 
+#include <stddef.h>
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -386,6 +388,27 @@ int nerfart_secant_update(const float* f_mid, int n_rays, float logit_tau, const
 int nerfart_root_finish(const float* rays_o, const float* rays_dn, int n_rays, const unsigned char* mask, const unsigned char* mask_start_outside,
                         const float* d_pred, const float* far, float far_s, int fill_inf, float* d_out, float* pt_out, void* stream);
 int nerfart_sphere_trace_step(const float* sdf, int n_rays, const float* far, float far_s, float* d, unsigned char* mask, void* stream);
+
+/* ---- isosurface extraction (utils/mesh_util.py:112 hands the SDF grid to skimage.measure.marching_cubes on the host;
+ * csrc/marching_cubes.hip: classify / scan / emit on the device, table-based marching cubes on the case table nerfart_amd/mc_table.py generates).
+ * An addition to ABI 5.  vol [nx, ny, nz] fp32, z fastest (mesh_util.sdf_volume's grid).  A corner is inside iff value < level; every vertex lies on a
+ * grid edge, owned by the edge's lower end point.
+ *   nerfart_mc_workspace_bytes: the size of the caller's workspace (0 = bad dimensions, see nerfart_last_error).
+ *   nerfart_mc_count: fills the workspace (per-point edge flags and case index, scanned vertex / triangle offsets) and counts [3] (DEVICE, 8-byte
+ *     aligned) = {V vertices, F triangles, 1 if any value of the volume is non-finite (such values count as outside)}.  Asynchronous.
+ *   nerfart_mc_emit: from the SAME, untouched workspace: verts [V, 3] on the sign-changing edges - with a, b the values at the edge's end points (a at the owner),
+ *     t = (level - a) / (b - a), pa = fma(index, spacing, origin), pb = fma(index + 1, spacing, origin) along the edge's axis, the vertex is
+ *     fma(t, pb - pa, pa) there and pa on the other two axes (fp32, each fma ONE rounding: what a second implementation must do to get the same
+ *     bits) - in the order (point in linear order, then axis x, y, z); faces [F, 3] int32 in the order (cell in linear order, then the table's
+ *     triangles), wound so that (v1 - v0) x (v2 - v0) points to the outside (value >= level).  origin / spacing: HOST arrays of 3.  V and F are the
+ *     sizes of the caller's arrays (every write is checked against them); V == 0 or F == 0 launches nothing.  No atomics: two runs are bit-identical.
+ * Refused with 2 before any launch: a null pointer, a dimension < 2, 3 nx ny nz >= 2^31, nx * ceil(ny / 4) * ceil(nz / 64) >= 2^24 (a volume
+ * long in x and thin in y / z: more blocks than one launch takes; put the long axis last), a workspace smaller than the query's answer (or not
+ * 16-byte aligned). */
+size_t nerfart_mc_workspace_bytes(int nx, int ny, int nz);
+int nerfart_mc_count(const float* vol, int nx, int ny, int nz, float level, void* ws, size_t ws_bytes, unsigned* counts, void* stream);
+int nerfart_mc_emit(const float* vol, int nx, int ny, int nz, float level, const float* origin, const float* spacing, const void* ws, size_t ws_bytes,
+                    float* verts, int* faces, unsigned V, unsigned F, void* stream);
 
 /* ---- VGG16 perceptual term (criteria/perp_loss.py:9-57): torchvision vgg16.features[:16] (through relu3_3) as
  * implicit-GEMM 3 x 3 convolutions on v_mfma_f32_32x32x2_f32 (fp32 operands as the reference's net; csrc/vgg_conv.hip), L1

@@ -130,6 +130,9 @@ _SIGS = {
     "nerfart_pack_layer_dims": (_i, [_i, _i, _p, _p]),
     "nerfart_geometry_feature_workspace_bytes": (_ll, []),
     "nerfart_geometry_feature": (_i, [_p, _p, _p, _p, _ll, _p, _p, _ll, _p]),
+    "nerfart_mc_workspace_bytes": (_ll, [_i, _i, _i]),
+    "nerfart_mc_count": (_i, [_p, _i, _i, _i, _f, _p, _ll, _p, _p]),
+    "nerfart_mc_emit": (_i, [_p, _i, _i, _i, _f, _p, _p, _p, _ll, _p, _p, _i, _i, _p]),
     "nerfart_pack_surface_blob": (_i, [_i, _i, _p, _p, _p, _p, _ll, _p, _ll, _p]),
     "nerfart_pack_radiance_blob": (_i, [_i, _i, _p, _p, _p, _p, _p, _p, _p, _ll, _p, _ll, _p]),
     "nerfart_pack_plan_debug": (_i, [_i, _i, _i] + [_p] * 6),
@@ -303,6 +306,41 @@ def geometry_feature(weight_g, weight_v, bias, h7):
                                         _dev(bias.detach().contiguous(), name="bias"), _dev(h7, name="h7"), M, _dev(out), ws.data_ptr(), ws.numel(), _stream()),
            "nerfart_geometry_feature")
     return out
+
+
+def _mc_volume(vol):
+    if vol.dim() != 3:
+        raise NerfartHipError(f"the volume must be [nx, ny, nz] (got {tuple(vol.shape)})")
+    return _dev(vol, name="vol"), [int(d) for d in vol.shape]
+
+
+def mc_workspace_bytes(nx: int, ny: int, nz: int) -> int:
+    """nerfart_mc_workspace_bytes; bad dimensions (one below 2, 3 nx ny nz >= 2^31) raise with the library's message."""
+    n = int(lib.nerfart_mc_workspace_bytes(nx, ny, nz))
+    _check(0 if n else 2, "nerfart_mc_workspace_bytes")
+    return n
+
+
+def mc_count(vol, level: float, ws=None):
+    """nerfart_mc_count on vol [nx, ny, nz]: (ws, counts) - the filled workspace (uint8; a caller's own, or a fresh one: it must stay untouched until
+    mc_emit has run) and the int32 device tensor counts [3] = (vertices, triangles, non-finite flag).  No host synchronisation."""
+    ptr, dims = _mc_volume(vol)
+    if ws is None:
+        ws = torch.empty(mc_workspace_bytes(*dims), dtype=torch.uint8, device=vol.device)
+    counts = torch.empty(3, dtype=torch.int32, device=vol.device)
+    _check(lib.nerfart_mc_count(ptr, *dims, float(level), _dev(ws, torch.uint8, "ws"), ws.numel(), counts.data_ptr(), _stream()), "nerfart_mc_count")
+    return ws, counts
+
+
+def mc_emit(vol, level: float, origin, spacing, ws, V: int, F: int):
+    """nerfart_mc_emit: (verts [V, 3] float32, faces [F, 3] int32) from the workspace mc_count filled for the same volume and level."""
+    ptr, dims = _mc_volume(vol)
+    verts = torch.empty(V, 3, dtype=torch.float32, device=vol.device)
+    faces = torch.empty(F, 3, dtype=torch.int32, device=vol.device)
+    o, s = (C.c_float * 3)(*[float(x) for x in origin]), (C.c_float * 3)(*[float(x) for x in spacing])
+    _check(lib.nerfart_mc_emit(ptr, *dims, float(level), C.cast(o, C.c_void_p), C.cast(s, C.c_void_p), _dev(ws, torch.uint8, "ws"), ws.numel(),
+                               verts.data_ptr(), faces.data_ptr(), V, F, _stream()), "nerfart_mc_emit")
+    return verts, faces
 
 
 def nabla_workspace(precision: int, device):

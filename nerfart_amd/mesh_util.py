@@ -8,8 +8,12 @@
     shears the y and x coordinates by up to one voxel, and calls `np.int` (removed from numpy 1.24 - the function no longer
     runs); the regular grid is evaluated here; `reference_shear=True` reproduces the sheared coordinates;
   * grid points are generated on the GPU and evaluated in chunks of millions of points (the reference: 16 K).
-`extract_mesh` itself needs skimage (marching cubes) and plyfile, both third-party and absent here: it is provided only if
-they import.
+
+`extract_mesh` runs natively by default: `sdf_volume` -> `marching_cubes` (csrc/marching_cubes.hip: classify / scan / emit on the device, the
+volume never leaves the GPU) -> `write_ply` (numpy only, the layout plyfile writes for the reference's two elements).  The native extractor is
+table-based marching cubes on the case table nerfart_amd/mc_table.py generates - not scikit-image's Lewiner variant: the surface is the same, the
+triangulation inside ambiguous cells differs ("deviations").  `backend="skimage"` keeps the reference's route through
+scikit-image and plyfile, for machines that have them.
 """
 import numpy as np
 import torch
@@ -40,12 +44,51 @@ def sdf_volume(implicit_surface, volume_size: float = 2.0, N: int = 512, chunk: 
     return out.reshape(N, N, N)
 
 
+def marching_cubes(vol, level: float = 0.0, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0)):
+    """Isosurface of vol [nx, ny, nz] (float32, on the GPU) at `level`: (verts [V, 3] float32, faces [F, 3] int32), both on vol's device.
+    A grid point (i, j, k) sits at origin + (i, j, k) * spacing; a point is inside iff its value < level, and the triangles are wound so that
+    (v1 - v0) x (v2 - v0) points to the outside (outward for a signed distance).  Vertex and face order are defined (points resp. cells in linear
+    order), so two calls give identical tensors.  One host read (the two sizes and the non-finite flag) sits between counting and emitting;
+    a non-finite value raises ValueError; no crossing gives (0, 3) tensors.  CPU tensors are refused: there is no CPU path."""
+    from . import hip                                              # here, not at import: grid_points and write_ply need no library
+    ws, counts = hip.mc_count(vol, level)
+    V, F, bad = (int(c) for c in counts.cpu())
+    if bad:
+        raise ValueError("marching_cubes: the volume holds non-finite values")
+    return hip.mc_emit(vol, level, origin, spacing, ws, V, F)
+
+
+def write_ply(path, verts, faces):
+    """Binary little-endian PLY: `element vertex` with float x, y, z and `element face` with `property list uchar int vertex_indices` - the file
+    plyfile writes for the reference's two elements (mesh_util.py:57-80).  verts [V, 3], faces [F, 3]: tensors or arrays."""
+    v = np.ascontiguousarray(verts.detach().cpu().numpy() if torch.is_tensor(verts) else verts, dtype="<f4").reshape(-1, 3)
+    f = np.asarray(faces.detach().cpu().numpy() if torch.is_tensor(faces) else faces).reshape(-1, 3)
+    rec = np.empty(len(f), dtype=[("n", "u1"), ("i", "<i4", (3,))])
+    rec["n"], rec["i"] = 3, f
+    header = ("ply\nformat binary_little_endian 1.0\n"
+              f"element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n"
+              f"element face {len(f)}\nproperty list uchar int vertex_indices\nend_header\n")
+    with open(path, "wb") as out:
+        out.write(header.encode("ascii"))
+        out.write(v.tobytes())
+        out.write(rec.tobytes())
+    return path
+
+
 def extract_mesh(implicit_surface, volume_size=2.0, level=0.0, N=512, filepath="./surface.ply", show_progress=True, chunk=1 << 24,
-                 reference_shear: bool = False):
-    """mesh_util.extract_mesh: SDF volume -> marching cubes -> .ply (needs skimage and plyfile).  reference_shear=True samples
+                 reference_shear: bool = False, backend: str = "native"):
+    """mesh_util.extract_mesh: SDF volume -> marching cubes -> .ply.  backend="native" (default): marching_cubes + write_ply above, nothing
+    third-party, the volume stays on the GPU; backend="skimage": the reference's route (needs scikit-image and plyfile).  Both place the mesh as
+    the reference does: spacing volume_size / N, offset -volume_size / 2 (mesh_util.py:112).  reference_shear=True samples
     the sheared grid the reference's true-division index arithmetic produces under Python 3 (vertex-for-vertex parity with its
     meshes); the default is the regular grid ("deviations").  show_progress is accepted for call compatibility:
     the sweep is a handful of kernel launches, there is nothing to show."""
+    if backend == "native":
+        vol = sdf_volume(implicit_surface, volume_size, N, chunk, reference_shear=reference_shear)
+        verts, faces = marching_cubes(vol, level=level, spacing=[volume_size / N] * 3, origin=[-volume_size / 2.0] * 3)
+        return write_ply(filepath, verts, faces)
+    if backend != "skimage":
+        raise ValueError(f"extract_mesh: backend must be 'native' or 'skimage' (got {backend!r})")
     try:
         from skimage import measure
         import plyfile

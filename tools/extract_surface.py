@@ -1,0 +1,46 @@
+#!/usr/bin/env python
+"""Counterpart of the reference's tools/extract_surface.py: config (+ checkpoint) -> SDF grid -> marching cubes -> .ply, all on
+the GPU (nerfart_amd.mesh_util.extract_mesh: the SDF kernel, csrc/marching_cubes.hip, a numpy PLY writer; nothing third-party).
+
+    python tools/extract_surface.py --config configs/volsdf.yaml --load_pt ckpts/latest.pt --N 512 --volume_size 2.0 --out surface.ply
+
+Without --load_pt the mesh is the model's sphere initialisation.  `--k1:k2 v` overrides of the config work as everywhere (nerfart_amd.config)."""
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def parse(argv=None):
+    """(args, config) from the command line: the reference's parser (--config / --resume_dir) plus this tool's options."""
+    from nerfart_amd import config as cfg
+    parser = cfg.create_args_parser()
+    parser.add_argument("--load_pt", type=str, default=None, help="checkpoint (torch.save({'model': state_dict, ...})); default: the initialisation")
+    parser.add_argument("--N", type=int, default=512, help="grid points per axis")
+    parser.add_argument("--volume_size", type=float, default=2.0, help="edge length of the cube, centred at the origin")
+    parser.add_argument("--level", type=float, default=0.0)
+    parser.add_argument("--chunk", type=int, default=1 << 24, help="grid points per SDF launch")
+    parser.add_argument("--out", type=str, default="surface.ply")
+    args, unknown = parser.parse_known_args(argv)
+    return args, cfg.load_config(args, unknown)
+
+
+def main():
+    from nerfart_amd import frameworks, mesh_util
+    args, conf = parse()
+    assert torch.cuda.is_available(), "extract_surface needs the GPU (nerfart_amd has no CPU path)"
+    dev = torch.device("cuda", conf.device_ids[0])
+    model = frameworks.get_model(conf)[0]
+    if args.load_pt is not None:
+        state = torch.load(args.load_pt, map_location="cpu")
+        model.load_state_dict(state["model"] if "model" in state else state)
+    model.to(dev)
+    path = mesh_util.extract_mesh(model.implicit_surface, volume_size=args.volume_size, level=args.level, N=args.N, filepath=args.out, chunk=args.chunk)
+    print(path)
+
+
+if __name__ == "__main__":
+    main()
