@@ -330,6 +330,115 @@ __global__ void k_scatter_samples(const int* __restrict__ list, int n, int n_fin
     if (t == 0) { beta_map[ray] = c_beta[slot]; iter_usage[ray] = c_iter[slot]; }
 }
 
+// ---- segment-ordered final stage (final_stage_skipping): the P final samples of a ray in depth segments of SKIP_SEG, front to back; a ray whose
+// transmittance has reached exactly 0 in fp32 leaves the live list and the samples behind that point are never evaluated -----------------------
+//
+// The rule.  x_k = fmaxf(sdf_to_sigma(sdf_k) * (d_{k+1} - d_k), 0) is the optical depth of interval k, the very expression k_composite_volsdf
+// exponentiates.  A ray is DEAD FROM SAMPLE s ON when the fp32 running sum of x_k over k < s, added in ascending k, is >= SKIP_THETA.
+// Why that makes every tau_k, k >= s, exactly +0 whatever sdf_k, nabla_k and radiance_k are (finite):
+//   - k_composite_volsdf forms T_k as a product of p_j = expf(-x_j), j < k: a lane-local product of ceil((P-1)/64) factors, the six levels of
+//     wave_excl_prod's shuffle tree, then `T *= p` inside the lane - about 12 multiplications deep for P = 192.  Every factor lies in [0, 1].
+//   - fp32 denormals are on: the smallest positive value is 2^-149 = e^-103.28 and a product rounds to 0 once it is below half of that, e^-103.97.
+//     A multiplication that lands in the denormal range can round UP, by at most x2 (e^0.69) per level; above it the error is 2^-24 relative.
+//     expf's own last-place error in the denormal range is another factor of at most 2.  So a computed T can be non-zero only if the exact
+//     product of the factors it contains is at least about e^(-103.97 - 13 * 0.69) = e^-113.
+//   - T_k for k >= s contains every factor j < s (and possibly more factors <= 1, which cannot raise it).  Their exact product is
+//     exp(-sum x_j), and the fp32 running sum differs from the exact sum by less than 0.01 at this size (P additions, ulp(128) = 1.5e-5).
+//   - THETA = 128 therefore leaves more than 14 units of margin over the 113 + 0.01 needed (tests/test_skip_threshold.py emulates the
+//     composite's product order over adversarial sequences).
+// With T_k = +0, tau_k = (1 - p_k + 1e-10f) * 0 = +0, and adding +0 (or the -0 of a negative nabla component times 0, to a sum that started at
+// +0) leaves every accumulator's bits unchanged; the product never recovers.  A NaN sum compares false: the ray stays alive, as before.
+// The samples not evaluated are ZERO-FILLED (sdf, nabla, radiance) when the ray is marked, so the composite - untouched - reads finite values
+// there whatever the workspace held (a caller may hand in a NaN-filled one: 0 * NaN would poison the pixel).
+enum { SKIP_SEG = 32 };
+constexpr float SKIP_THETA = 128.0f;
+
+__global__ void k_live_init(int c0, int n, int* __restrict__ live, float* __restrict__ osum) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) { live[i] = c0 + i; osum[c0 + i] = 0.f; }
+}
+
+// compact depth block [n_live, len] of the segment's samples e0 .. e0 + len - 1 of the listed rays
+__global__ void k_gather_segment_depths(const int* __restrict__ live, int n_live, int P, int e0, int len, const float* __restrict__ d_all,
+                                        float* __restrict__ c_d) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)n_live * len) return;
+    const int slot = (int)(i / len), j = (int)(i - (long long)slot * len);
+    c_d[i] = d_all[(size_t)live[slot] * P + e0 + j];
+}
+
+// slot-major compact outputs of a segment launch -> their [R, P] places
+__global__ void k_scatter_segment(const int* __restrict__ live, int n_live, int P, int e0, int len, const float* __restrict__ c_sdf,
+                                  const float* __restrict__ c_nabla, const float* __restrict__ c_rad, float* __restrict__ sdf,
+                                  float* __restrict__ nabla, float* __restrict__ rad) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)n_live * len) return;
+    const int slot = (int)(i / len), j = (int)(i - (long long)slot * len);
+    const size_t q = (size_t)live[slot] * P + e0 + j;
+    sdf[q] = c_sdf[i];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { nabla[3 * q + c] = c_nabla[3 * (size_t)i + c]; rad[3 * q + c] = c_rad[3 * (size_t)i + c]; }
+}
+
+// After segment [e0, e0 + len) is in place: one wave per live ray adds x_k, k = e0 .. e0 + len - 1 (every interval that starts inside the
+// segment; len <= SKIP_SEG < 64, and e0 + len < P here, so d_{k+1} exists), to the ray's running optical depth - lane j computes x_{e0+j}, the
+// sum itself runs in ascending k as one fp32 chain - and decides the rule above for s = e0 + len.  A ray found dead has its samples s .. P - 1
+// zero-filled.  alive[slot] = 0 / 1 feeds k_compact_live.
+__global__ void __launch_bounds__(256)
+k_advance_live(const int* __restrict__ live, int n_live, int P, int e0, int len, const float* __restrict__ d_all, float alpha, float beta,
+               float* __restrict__ osum, int* __restrict__ alive, float* sdf, float* __restrict__ nabla, float* __restrict__ rad) {
+    const int slot = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (slot >= n_live) return;                                   // wave-uniform
+    const int ray = live[slot];
+    const float* dr = d_all + (size_t)ray * P;
+    const float* sr = sdf + (size_t)ray * P;
+    float x = 0.f;
+    if (lane < len) {
+        const int k = e0 + lane;
+        x = fmaxf(sdf_to_sigma(sr[k], alpha, beta) * (dr[k + 1] - dr[k]), 0.f);
+    }
+    float sum = osum[ray];
+    for (int j = 0; j < len; ++j) sum = __fadd_rn(sum, __shfl(x, j, 64));
+    const bool dead = sum >= SKIP_THETA;
+    if (lane == 0) { osum[ray] = sum; alive[slot] = dead ? 0 : 1; }
+    if (dead) {
+        const size_t q0 = (size_t)ray * P + e0 + len;
+        const int n = P - (e0 + len);
+        for (int i = lane; i < n; i += 64) sdf[q0 + i] = 0.f;
+        for (int i = lane; i < 3 * n; i += 64) { nabla[3 * q0 + i] = 0.f; rad[3 * q0 + i] = 0.f; }
+    }
+}
+
+// Stable compaction of the live list (ascending ray order is kept, so a run is reproducible): block b owns slots [1024 b, 1024 b + 1024); its base
+// is the number of alive slots before them, counted by the block itself; ranks inside the block by ballot + LDS.  The last block writes the count.
+__global__ void __launch_bounds__(1024)
+k_compact_live(const int* __restrict__ live, const int* __restrict__ alive, int n_live, int* __restrict__ live_next, int* __restrict__ n_next) {
+    __shared__ int wsum[16];
+    __shared__ int base_sh;
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int first = blockIdx.x * 1024;
+    int part = 0;
+    for (int i = t; i < first; i += 1024) part += alive[i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
+    if (lane == 0) wsum[wv] = part;
+    __syncthreads();
+    if (t == 0) { int b = 0; for (int w = 0; w < 16; ++w) b += wsum[w]; base_sh = b; }
+    __syncthreads();
+    const int base = base_sh;
+    const int slot = first + t;
+    const bool keep = slot < n_live && alive[slot] != 0;
+    const unsigned long long mask = __ballot(keep);
+    const int rank = __popcll(mask & ((1ull << lane) - 1ull));
+    __syncthreads();                                              // wsum is reused
+    if (lane == 0) wsum[wv] = __popcll(mask);
+    __syncthreads();
+    int before = 0, total = 0;
+    for (int w = 0; w < 16; ++w) { const int c = wsum[w]; if (w < wv) before += c; total += c; }
+    if (keep) live_next[base + before + rank] = live[slot];
+    if (t == 0 && first + 1024 >= n_live) *n_next = base + total;
+}
+
 }  // namespace nerfart
 
 using namespace nerfart;
@@ -694,6 +803,44 @@ typedef struct {
     size_t nabla_ws_bytes;
 } render_ws_t;
 
+// Buffers of the segment-ordered final stage (final_stage_skipping): the live lists of a ray group, alive flags, the live count, the per-ray running
+// optical depths, and the compact depth / sdf / nabla / radiance blocks of one segment launch.  They are carved out of the SAMPLER's region of the
+// render workspace: Algorithm 1 has finished by then and its rows (16 bytes x 512 (1 + rounds) per ray) are dead, so the workspace does not grow.
+typedef struct {
+    int *live0, *live1, *alive, *n_live;
+    float *osum, *c_depth, *c_sdf, *c_nabla, *c_rad;
+} skip_ws_t;
+
+static skip_ws_t carve_skip(Carver& c, int R, int P, int G) {
+    skip_ws_t k;
+    const size_t gpts = (size_t)G * (P < SKIP_SEG ? P : SKIP_SEG);
+    k.live0 = c.take<int>((size_t)G);
+    k.live1 = c.take<int>((size_t)G);
+    k.alive = c.take<int>((size_t)G);
+    k.n_live = c.take<int>(1);
+    k.osum = c.take<float>((size_t)R);
+    k.c_depth = c.take<float>(gpts);
+    k.c_sdf = c.take<float>(gpts);
+    k.c_nabla = c.take<float>(gpts * 3);
+    k.c_rad = c.take<float>(gpts * 3);
+    return k;
+}
+
+// Rays per group: one segment launch of a full group has (about) as many points as one launch of the plain loop, G * min(SKIP_SEG, P) <=
+// min(k3_rays, R) * P, so the h7 carve holds it as it is (P = 192: G = 6 k3_rays) - halved until the buffers above fit the sampler's region
+// (they do at once for every reference configuration; with one ray per group they always do: the sampler holds several [R] arrays itself).
+static int skip_group_rays(int R, int P, int k3_rays, size_t room) {
+    const long long rk = k3_rays < R ? k3_rays : R;
+    long long g = rk * P / (P < SKIP_SEG ? P : SKIP_SEG);
+    if (g > R) g = R;
+    for (; g > 1; g /= 2) {
+        Carver c(nullptr);
+        carve_skip(c, R, P, (int)g);
+        if (c.off <= room) break;
+    }
+    return (int)g;
+}
+
 static render_ws_t carve_render(Carver& c, int R, int n_samples, int n_imp, int max_iter, int k3_rays) {
     render_ws_t w;
     const int P = n_samples + n_imp;
@@ -723,6 +870,48 @@ long long nerfart_volsdf_render_workspace_bytes(int n_rays, int n_samples, int n
     Carver c(nullptr);
     carve_render(c, n_rays, n_samples, n_importance, max_upsample_steps, k3_rays_chunk);
     return (long long)c.off;
+}
+
+// The final samples of every ray WITHOUT the ones behind full opacity (the rule and its derivation: next to SKIP_THETA).  Rays in groups
+// (skip_group_rays); per group the depth segments front to back: gather the live rays' depths of the segment, sdf + nabla and radiance on the live
+// list (slot-major compact outputs), scatter to [R, P], then advance the running optical depths, mark and zero-fill the dead, and compact the
+// list (stable: ascending ray order).  The live count reaches the host with ONE 4-byte read per segment per group (as the sampler's rounds do);
+// no live ray left ends the group; there are no zero-size launches.  Every stored value of an evaluated sample is what the plain loop stores.
+static int final_stage_skipping(const render_ws_t& w, const float* surf_blob, int precision, const float* rad_blob, int rad_precision, int view_tiles,
+                                const float* rays_o, int n_rays, int P, float R_bg, float alpha, float beta, const float* d_all, float* sdf,
+                                float* nabla, float* rad, int k3_rays, hipStream_t stream) {
+    const int G = skip_group_rays(n_rays, P, k3_rays, w.sampler_bytes);
+    Carver carver(w.sampler);
+    const skip_ws_t k = carve_skip(carver, n_rays, P, G);
+    if (carver.off > w.sampler_bytes) { set_last_error("render: workspace too small"); return 2; }
+    int *live = k.live0, *live_next = k.live1;
+    for (int c0 = 0; c0 < n_rays; c0 += G) {
+        int n_live = (n_rays - c0 < G) ? n_rays - c0 : G;
+        hipLaunchKernelGGL(k_live_init, dim3((n_live + 255) / 256), dim3(256), 0, stream, c0, n_live, live, k.osum);
+        NERFART_HIP(hipGetLastError());
+        for (int e0 = 0; e0 < P && n_live > 0; e0 += SKIP_SEG) {
+            const int len = (P - e0 < SKIP_SEG) ? P - e0 : SKIP_SEG;
+            const unsigned nb = (unsigned)(((long long)n_live * len + 255) / 256);
+            hipLaunchKernelGGL(k_gather_segment_depths, dim3(nb), dim3(256), 0, stream, live, n_live, P, e0, len, d_all, k.c_depth);
+            NERFART_HIP(hipGetLastError());
+            if (int rc = nerfart_sdf_nabla_fwd_rays(surf_blob, precision, rays_o, w.rays_dn, live, k.c_depth, n_live, len, len, R_bg, k.c_sdf, k.c_nabla,
+                                                    w.h7, w.nabla_ws, (long long)w.nabla_ws_bytes, stream)) return rc;
+            if (int rc = nerfart_radiance_fwd_rays(rad_blob, rad_precision, view_tiles, rays_o, w.rays_dn, live, k.c_depth, n_live, len, len, k.c_nabla,
+                                                   w.h7, k.c_rad, stream)) return rc;
+            hipLaunchKernelGGL(k_scatter_segment, dim3(nb), dim3(256), 0, stream, live, n_live, P, e0, len, k.c_sdf, k.c_nabla, k.c_rad, sdf, nabla, rad);
+            NERFART_HIP(hipGetLastError());
+            if (e0 + len >= P) break;                                 // the last segment: nothing behind it to skip
+            hipLaunchKernelGGL(k_advance_live, dim3((n_live + 3) / 4), dim3(256), 0, stream, live, n_live, P, e0, len, d_all, alpha, beta, k.osum,
+                               k.alive, sdf, nabla, rad);
+            NERFART_HIP(hipGetLastError());
+            hipLaunchKernelGGL(k_compact_live, dim3((n_live + 1023) / 1024), dim3(1024), 0, stream, live, k.alive, n_live, live_next, k.n_live);
+            NERFART_HIP(hipGetLastError());
+            NERFART_HIP(hipMemcpyAsync(&n_live, k.n_live, sizeof(int), hipMemcpyDeviceToHost, stream));
+            NERFART_HIP(hipStreamSynchronize(stream));
+            int* t = live; live = live_next; live_next = t;
+        }
+    }
+    return 0;
 }
 
 // Renders n_rays rays (rays_d un-normalised, as get_rays returns them).  Outputs rgb [R,3], depth [R],
@@ -771,7 +960,13 @@ int nerfart_volsdf_render_staged2_fwd(const float* surf_blob, int precision, con
     }
     if (int rc = nerfart_linspace_depths(w.t_coarse, n_samples, nullptr, nullptr, near_s, far_s, n_rays, w.d_coarse, n_samples, stream)) return rc;
     if (int rc = nerfart_sort_concat(n_rays, w.d_coarse, n_samples, n_samples, w.d_fine, n_importance, n_importance, d_all, P, stream)) return rc;
-    for (int c0 = 0; c0 < n_rays; c0 += k3_rays_chunk) {
+    // no per-sample output asked for: the samples behind full opacity reach no output and are not evaluated (final_stage_skipping); with any of
+    // them the plain loop evaluates every sample, so the detailed outputs stay the reference's everywhere
+    const bool skipping = !sdf_out && !nabla_out && !radiance_out && !sigma_out && !p_out && !tau_out;
+    if (skipping)
+        if (int rc = final_stage_skipping(w, surf_blob, precision, rad_blob, rad_precision, view_tiles, rays_o, n_rays, P, R_bg, alpha, beta, d_all, sdf,
+                                          nabla, rad, k3_rays_chunk, stream)) return rc;
+    for (int c0 = 0; c0 < n_rays && !skipping; c0 += k3_rays_chunk) {
         const int rk = (n_rays - c0 < k3_rays_chunk) ? n_rays - c0 : k3_rays_chunk;
         const size_t po = (size_t)c0 * P;
         if (int rc = nerfart_sdf_nabla_fwd_rays(surf_blob, precision, rays_o + 3 * (size_t)c0, w.rays_dn + 3 * (size_t)c0, nullptr,

@@ -1,6 +1,8 @@
 #!/usr/bin/env python
 """How many of the 192 final samples of a ray lie behind the point where the transmittance has underflowed (their weights are 0:
-the renderer's rgb / depth / normals do not depend on them)?  Benchmark scene, 480x270, strided rays; segment-granular fractions."""
+the renderer's rgb / depth / normals do not depend on them)?  Benchmark scene, 480x270, strided rays; segment-granular fractions.
+Row `rule_theta128_seg32`: what the renderer's segment-ordered final stage skips (csrc/volsdf_render.hip: the fp32 running optical depth, added in
+ascending k, checked against THETA = 128 at the 32-sample segment boundaries; a dead ray's remaining segments, the shorter last one included)."""
 import json, os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -31,6 +33,16 @@ for beta in (0.01, 0.002, 0.1):
             ns = P // seg
             dseg = dead[:, :ns * seg].reshape(-1, ns, seg).all(dim=2)     # whole segment dead
             res[name][f"segments_of_{seg}_dead_frac"] = round(float(dseg.float().mean()), 4)
+    # the rule as built: fp32 chain, THETA = 128, decided at s = 32, 64, ... (every sample from s on is skipped)
+    x32 = torch.relu(ex["sigma"][0][:, :-1] * (ex["d_vals"][0][:, 1:] - ex["d_vals"][0][:, :-1]))
+    run = torch.zeros_like(x32[:, 0])
+    evaluated = torch.full_like(run, P)
+    for k in range(P - 1):
+        run = run + x32[:, k]
+        if (k + 1) % 32 == 0 and k + 1 < P:
+            evaluated = torch.where((run >= 128.0) & (evaluated == P), torch.full_like(evaluated, k + 1), evaluated)
+    res["rule_theta128_seg32"] = {"points_skipped_frac": round(float(1.0 - evaluated.mean() / P), 4),
+                                  "rays_with_a_skipped_segment_frac": round(float((evaluated < P).float().mean()), 4)}
     res["rays_hitting"] = round(float((logT[:, -1] < -69).float().mean()), 4)
     out[f"beta_{beta}"] = res
 print(json.dumps(out))
