@@ -9,9 +9,10 @@
 // arithmetic).  A rounded weight is a FIXED, smooth perturbation of the SDF (~2^-12 relative per weight), not point-to-point noise: the hidden
 // activations' 11 bits already set the sampler's resolution (tools/emul_sampler_precision.py: sdf error mean 1.55e-4 against the 2-MFMA form's 1.36e-4).
 // No other entry point accepts precision 5: no value that reaches a pixel and no gradient is ever computed in it.
+// This k-step-outer kernel is the REFERENCE of precision 5 (sdf_f16x1_ref): mlp_k2_f16x1_to.hip holds the launcher sdf_f16x1 and the tile-outer kernel.
 #define NERFART_F16X2 1
 #define NERFART_F16X1 1
 #define NERFART_K2_ONLY 1
 #define b16 f16x1
-#define sdf_bf16_v1 sdf_f16x1
+#define sdf_bf16_v1 sdf_f16x1_ref
 #include "mlp_chain_bf16.hip"

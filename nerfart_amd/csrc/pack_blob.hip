@@ -136,6 +136,9 @@ __host__ __device__ inline Chunk chunk_desc(const Prog& p, int c) {
         if (c < 30 || c >= 63) {                        // forward layers: 16x16x32 fragments (chunks 0..29) / 32x32x16 fragments (63..92)
             const bool w32 = c >= 63;
             if (w32) c -= 63;
+            // mlp_k2_f16x1_to.hip relies on chunks 0..29 as they are numbered here (a layer's first chunk: 0, 1, 5, 9, 13, 18, 22, 26 = its to_first_chunk) AND on a
+            // layer's chunks lying back to back in the blob (Layout.offs is a running sum), so that item (k-step u, tile T) of a layer sits at the layer's first
+            // offset + (16 u + T) * 512 floats: tests/test_k2_tile_outer_layout.py holds both against the header this file writes
             int l, k;
             if (c < 1) { l = 0; k = 0; } else if (c < 13) { l = 1 + (c - 1) / 4; k = (c - 1) % 4; } else if (c < 18) { l = 4; k = c - 13; } else { l = 5 + (c - 18) / 4; k = (c - 18) % 4; }
             d.tensor = 2 * l; d.out_dim = surf_dims(l).rows; d.limit = surf_dims(l).cols;

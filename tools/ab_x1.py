@@ -48,6 +48,7 @@ def run(names):
     outs = {}
     for name in ["main"] + names + ["main"]:
         env = dict(os.environ)
+        env["NERFART_K2_F16X1"] = "ref"             # the variants are builds of the k-step-outer kernel: precision 5's default is mlp_k2_f16x1_to.hip
         if name != "main":
             env["NERFART_HIP_LIB"] = os.path.join(OUT, f"libx1_{name}.so")
         path = f"/tmp/abx1_{name}.pt"
