@@ -10,6 +10,7 @@
 // k_merge_check 1.13 -> 1.07 ms per launch; the kernel waits on its exp / divide chains, as round 2 found.)
 #pragma once
 #include "nerfart_common.h"
+#include "sample_cdf.h"
 #include <math.h>
 
 namespace nerfart {
@@ -51,39 +52,6 @@ __device__ __forceinline__ float wave_excl_prod(float v) {
 __device__ __forceinline__ float sdf_to_sigma(float s, float alpha, float beta) {
     const float e = 0.5f * expf(-fabsf(s) / beta);
     return alpha * ((s >= 0.f) ? e : 1.f - e);
-}
-
-// first index i in [0, n] with c[i] >= u  (torch.searchsorted(..., right=False))
-__device__ __forceinline__ int lower_bound(const float* c, int n, float u) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (c[mid] < u) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-// first index i in [0, n] with c[i] > u
-__device__ __forceinline__ int upper_bound(const float* c, int n, float u) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (c[mid] <= u) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// Piece-wise linear inverse CDF of one sample (utils/rend_util.py:276-291): bracket by lower
-// bound, clamp to the array, a denominator below 1e-5 becomes 1.
-__device__ __forceinline__ float invert_cdf_at(const float* bins, const float* cdf, int n, float u) {
-    const int idx = lower_bound(cdf, n, u);
-    const int below = idx - 1 < 0 ? 0 : idx - 1;
-    const int above = idx > n - 1 ? n - 1 : idx;
-    const float c0 = cdf[below], c1 = cdf[above];
-    float denom = c1 - c0;
-    if (denom < 1e-5f) denom = 1.f;
-    const float t = (u - c0) / denom;
-    const float b0 = bins[below], b1 = bins[above];
-    return b0 + t * (b1 - b0);
 }
 
 // a12 error_bound (volsdf.py:56-94) of the n-1 intervals of one ray held in LDS.

@@ -11,6 +11,7 @@
 // One 4-byte device->host read of the active count per round is the only host synchronisation.
 #include "ray_common.h"
 #include "host_util.h"
+#include <cstdlib>
 
 namespace nerfart {
 
@@ -97,11 +98,13 @@ k_first_check(SamplerParams P, const float* __restrict__ dA, const float* __rest
 }
 
 // Up-sample an active ray: 512 new depths by inverting the CDF of the current error bound
-// (sample_pdf(d, bounds, N_up + 2, det=True)[1:-1], volsdf.py:196), sorted.
+// (sample_pdf(d, bounds, N_up + 2, det=True)[1:-1], volsdf.py:196), sorted.  The inversion of an ascending u over one CDF comes out ascending except
+// for last-place effects at bin boundaries and NaN rows: the 45-stage sort runs only for a row that fails lane_row_in_order (sample_cdf.h), or always
+// (always_sort: NERFART_UPSAMPLE_SORT=always) - the same bits either way.
 __global__ void __launch_bounds__(64)
 k_upsample(SamplerParams P, const float* __restrict__ dA, const float* __restrict__ sA,
            const int* __restrict__ act, const float* __restrict__ beta_plus, const float* __restrict__ u_up,
-           int clamp_bounds, float* __restrict__ d_new) {
+           int clamp_bounds, int always_sort, float* __restrict__ d_new) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int slot = blockIdx.x, ray = act[slot];
     const int n = P.n;
@@ -127,7 +130,8 @@ k_upsample(SamplerParams P, const float* __restrict__ dA, const float* __restric
     for (int k = k0; k < k1; ++k) { run += w[k] / total; cdf[k + 1] = run; }
     __syncthreads();
     for (int j = lane; j < P.n_up; j += 64) out[j] = invert_cdf_at(d, cdf, n, u_up[j + 1]);
-    bitonic_sort(out, P.n_up);
+    __syncthreads();
+    if (always_sort || !__all((int)lane_row_in_order(out, P.n_up, lane))) bitonic_sort(out, P.n_up);
     for (int j = lane; j < P.n_up; j += 64) d_new[(size_t)slot * P.n_up + j] = out[j];
 }
 
@@ -519,8 +523,11 @@ static int upsample_launch(int n_active, int n, int cap, int n_up, const float* 
     SamplerParams P{n, cap, n_up, 0, 0, 0, 0.f, 0.f, 0.f};
     const size_t lds = ((size_t)4 * n + n_up) * sizeof(float);
     if (int rc = set_lds((const void*)k_upsample, lds, kLdsRefusal)) return rc;
+    // NERFART_UPSAMPLE_SORT=always sorts every row; read at every call, so that one process can run both (tests/test_gpu_upsample_sorted.py)
+    const char* e = std::getenv("NERFART_UPSAMPLE_SORT");
+    const int always_sort = (e != nullptr && e[0] == 'a') ? 1 : 0;
     hipLaunchKernelGGL(k_upsample, dim3(n_active), dim3(64), lds, (hipStream_t)stream, P, dA, sA, act, beta_plus, u_up,
-                       clamp_bounds, d_new);
+                       clamp_bounds, always_sort, d_new);
     NERFART_HIP(hipGetLastError());
     return 0;
 }
