@@ -410,6 +410,37 @@ int nerfart_mc_count(const float* vol, int nx, int ny, int nz, float level, void
 int nerfart_mc_emit(const float* vol, int nx, int ny, int nz, float level, const float* origin, const float* spacing, const void* ws, size_t ws_bytes,
                     float* verts, int* faces, unsigned V, unsigned F, void* stream);
 
+/* ---- mesh vertices on their grid edges (csrc/marching_cubes.hip, csrc/mesh_vertices.hip; mesh_util.refine_vertices): which edge a vertex of
+ * nerfart_mc_emit sits on, its position from the edge parameter t, and a refinement of t against the SDF that never leaves the edge - so faces stay
+ * valid unchanged.  Additions to ABI 5; no counterpart in the reference.  One thread per vertex, no atomics: two runs give the same bits.  V == 0
+ * launches nothing and returns 0; a null pointer is refused with 2.
+ *   nerfart_mc_emit_edges: from the SAME, untouched workspace nerfart_mc_count filled, in nerfart_mc_emit's vertex order (point in linear order,
+ *     then axis x, y, z, at the scanned offset), every write checked against V.  For vertex i on the edge owned by point p (linear index) toward
+ *     +axis, with a = vol[p], b = vol[p + stride[axis]]:
+ *       edge[i] = 3 p + axis (uint32);  bracket[i] = (t0, g0, t1, g1) = (0, a - level, 1, b - level) ([V, 4] fp32);
+ *       t[i] = (level - a) / (b - a), nerfart_mc_emit's expression;  best[i] = (t_best, g_best) = (t[i], +inf) ([V, 2] fp32);  side[i] = 0 (uint8).
+ *     Refusals as nerfart_mc_emit: dimensions, workspace size and alignment.
+ *   nerfart_mesh_edge_points: pts_out [V, 3] in the frame origin / spacing (HOST arrays of 3), with nerfart_mc_emit's arithmetic: idx = the
+ *     point's (x, y, z), pa[c] = fma(idx[c], spacing[c], origin[c]), pb = fma(idx[axis] + 1, spacing[axis], origin[axis]),
+ *     q[axis] = fma(t, pb - pa[axis], pa[axis]), the other two components pa - so t as nerfart_mc_emit_edges left it and the same frame give
+ *     nerfart_mc_emit's verts bit for bit.  An edge whose point index is >= nx ny nz, or whose far end is outside the volume, writes nothing for
+ *     that vertex (and nothing is read or written out of bounds).  Refused: a dimension < 2, 3 nx ny nz >= 2^31.
+ *   nerfart_mesh_edge_refine_step: one step of bracket-keeping false position with the Illinois modification.  f [V] = the SDF at the points of
+ *     the current t.  Per vertex, with g = f - level, in this order (fp32, every operation rounded once, in the order written):
+ *       1. if |g| < |g_best|: best = (t, g).  NaN never wins; the first finite evaluation always does.
+ *       2. if g is NaN: nothing else of this vertex changes.
+ *       3. if g == 0: bracket = (t, 0, t, 0), side = 0, t stays.
+ *       4. if (g < 0) == (g0 < 0): if side == 1, g1 *= 0.5; then (t0, g0) = (t, g), side = 1.
+ *          else:                   if side == 2, g0 *= 0.5; then (t1, g1) = (t, g), side = 2.
+ *       5. t = t0 - (g0 * (t1 - t0)) / (g1 - g0); a non-finite result becomes 0.5 * (t0 + t1); the result is clamped into
+ *          [min(t0, t1), max(t0, t1)].
+ *     The refined vertex is t_best: its residual g_best was actually evaluated, |g_best| never grows, and t, t_best stay in [0, 1]. */
+int nerfart_mc_emit_edges(const float* vol, int nx, int ny, int nz, float level, const void* ws, size_t ws_bytes, unsigned* edge, float* bracket,
+                          float* t, float* best, unsigned char* side, unsigned V, void* stream);
+int nerfart_mesh_edge_points(const unsigned* edge, const float* t, unsigned V, int nx, int ny, int nz, const float* origin, const float* spacing,
+                             float* pts_out, void* stream);
+int nerfart_mesh_edge_refine_step(const float* f, float level, unsigned V, float* bracket, float* t, float* best, unsigned char* side, void* stream);
+
 /* ---- VGG16 perceptual term (criteria/perp_loss.py:9-57): torchvision vgg16.features[:16] (through relu3_3) as
  * implicit-GEMM 3 x 3 convolutions on v_mfma_f32_32x32x2_f32 (fp32 operands as the reference's net; csrc/vgg_conv.hip), L1
  * between prediction and target features.

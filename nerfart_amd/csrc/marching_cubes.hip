@@ -11,7 +11,10 @@
 //   k_mc_emit      a point writes its vertices at its scanned offset in axis order; a cell writes its triangles at its scanned offset in table
 //                  order, a vertex index being the owner's scanned offset + the rank of the edge among the owner's flagged edges.  No atomics:
 //                  the output is a pure function of the volume, so two runs are bit-identical.  Every write is checked against V / F.
+//   k_mc_emit_edges  the same walk, writing per vertex which grid edge it sits on and the initial state of the vertex refinement
+//                  (csrc/mesh_vertices.hip) instead of a position.
 #include "host_util.h"
+#include <cmath>
 #include <string>
 #define MC_TABLE_DECL static __device__ const
 #include "mc_table.h"
@@ -194,6 +197,42 @@ __global__ void __launch_bounds__(256) k_mc_emit(const float* __restrict__ vol, 
     }
 }
 
+// The edge records of k_mc_emit's vertices, in its order (the tile and the walk of k_mc_emit): vertex i on the edge point p owns toward +axis gets
+// edge = 3 p + axis, the bracket (0, a - level, 1, b - level) of the edge parameter, t = k_mc_emit's very expression, best = (t, +inf), side = 0 -
+// the initial state of the refinement in csrc/mesh_vertices.hip.  Same guards as k_mc_emit: a foreign workspace gives wrong records, no access
+// outside the buffers.
+__global__ void __launch_bounds__(256) k_mc_emit_edges(const float* __restrict__ vol, int nx, int ny, int nz, float level, int by, int bz,
+                                                       const unsigned char* __restrict__ flags, const uint2* __restrict__ off,
+                                                       unsigned* __restrict__ edge, float* __restrict__ bracket, float* __restrict__ t_out,
+                                                       float* __restrict__ best, unsigned char* __restrict__ side, unsigned V) {
+    int x, ty, tz;
+    mc_tile(by, bz, x, ty, tz);
+    const int z = tz * MC_TILE_Z + (threadIdx.x & 63), y = ty * MC_TILE_Y + (threadIdx.x >> 6);
+    if (z >= nz || y >= ny) return;
+    const size_t stride[3] = {(size_t)ny * nz, (size_t)nz, 1};
+    const size_t p = (size_t)x * stride[0] + (size_t)y * stride[1] + z;
+    const unsigned f = flags[p] & 7u;
+    if (!f) return;
+    const int idx[3] = {x, y, z}, dim[3] = {nx, ny, nz};
+    const float a = vol[p];
+    unsigned vi = off[p].x;
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) {
+        if (!((f >> ax) & 1u)) continue;
+        if (idx[ax] + 1 < dim[ax] && vi < V) {
+            const float b = vol[p + stride[ax]];
+            const float t = (level - a) / (b - a);
+            edge[vi] = 3u * (unsigned)p + (unsigned)ax;
+            float* br = bracket + 4 * (size_t)vi;
+            br[0] = 0.f; br[1] = a - level; br[2] = 1.f; br[3] = b - level;
+            t_out[vi] = t;
+            best[2 * (size_t)vi] = t; best[2 * (size_t)vi + 1] = INFINITY;
+            side[vi] = 0;
+        }
+        ++vi;
+    }
+}
+
 // 0 = fine; else the refusal is in last_error
 static int mc_check_dims(const char* who, int nx, int ny, int nz) {
     char msg[200];
@@ -282,6 +321,21 @@ int nerfart_mc_emit(const float* vol, int nx, int ny, int nz, float level, const
     const int by = (ny + MC_TILE_Y - 1) / MC_TILE_Y, bz = (nz + MC_TILE_Z - 1) / MC_TILE_Z;
     hipLaunchKernelGGL(k_mc_emit, dim3((unsigned)((size_t)nx * by * bz)), dim3(256), 0, (hipStream_t)stream, vol, nx, ny, nz, level, by, bz, fr,
                        (const unsigned char*)w.flags, (const unsigned char*)w.cases, (const uint2*)w.off, verts, faces, V, F);
+    NERFART_HIP(hipGetLastError());
+    return 0;
+}
+
+int nerfart_mc_emit_edges(const float* vol, int nx, int ny, int nz, float level, const void* ws, size_t ws_bytes, unsigned* edge, float* bracket,
+                          float* t, float* best, unsigned char* side, unsigned V, void* stream) {
+    if (V == 0) return 0;
+    if (!vol || !ws || !edge || !bracket || !t || !best || !side) { set_last_error("mc_emit_edges: null pointer"); return 2; }
+    if (int rc = mc_check_dims("mc_emit_edges", nx, ny, nz)) return rc;
+    const size_t n = (size_t)nx * ny * nz;
+    if (int rc = mc_check_workspace("mc_emit_edges", ws, ws_bytes, mc_carve(nullptr, n).bytes)) return rc;
+    const McWorkspace w = mc_carve(const_cast<void*>(ws), n);
+    const int by = (ny + MC_TILE_Y - 1) / MC_TILE_Y, bz = (nz + MC_TILE_Z - 1) / MC_TILE_Z;
+    hipLaunchKernelGGL(k_mc_emit_edges, dim3((unsigned)((size_t)nx * by * bz)), dim3(256), 0, (hipStream_t)stream, vol, nx, ny, nz, level, by, bz,
+                       (const unsigned char*)w.flags, (const uint2*)w.off, edge, bracket, t, best, side, V);
     NERFART_HIP(hipGetLastError());
     return 0;
 }

@@ -133,6 +133,9 @@ _SIGS = {
     "nerfart_mc_workspace_bytes": (_ll, [_i, _i, _i]),
     "nerfart_mc_count": (_i, [_p, _i, _i, _i, _f, _p, _ll, _p, _p]),
     "nerfart_mc_emit": (_i, [_p, _i, _i, _i, _f, _p, _p, _p, _ll, _p, _p, _i, _i, _p]),
+    "nerfart_mc_emit_edges": (_i, [_p, _i, _i, _i, _f, _p, _ll, _p, _p, _p, _p, _p, _i, _p]),
+    "nerfart_mesh_edge_points": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p]),
+    "nerfart_mesh_edge_refine_step": (_i, [_p, _f, _i, _p, _p, _p, _p, _p]),
     "nerfart_pack_surface_blob": (_i, [_i, _i, _p, _p, _p, _p, _ll, _p, _ll, _p]),
     "nerfart_pack_radiance_blob": (_i, [_i, _i, _p, _p, _p, _p, _p, _p, _p, _ll, _p, _ll, _p]),
     "nerfart_pack_plan_debug": (_i, [_i, _i, _i] + [_p] * 6),
@@ -341,6 +344,49 @@ def mc_emit(vol, level: float, origin, spacing, ws, V: int, F: int):
     _check(lib.nerfart_mc_emit(ptr, *dims, float(level), C.cast(o, C.c_void_p), C.cast(s, C.c_void_p), _dev(ws, torch.uint8, "ws"), ws.numel(),
                                verts.data_ptr(), faces.data_ptr(), V, F, _stream()), "nerfart_mc_emit")
     return verts, faces
+
+
+def mc_emit_edges(vol, level: float, ws, V: int):
+    """nerfart_mc_emit_edges: the edge records of mc_emit's V vertices, in its order, from the same untouched workspace -
+    (edge [V] int32 holding the uint32 3 p + axis, bracket [V, 4], t [V], best [V, 2], side [V] uint8): the initial state of mesh_edge_refine_step."""
+    ptr, dims = _mc_volume(vol)
+    dev = vol.device
+    edge = torch.empty(V, dtype=torch.int32, device=dev)
+    bracket, t, best = (torch.empty(V, 4, dtype=torch.float32, device=dev), torch.empty(V, dtype=torch.float32, device=dev),
+                        torch.empty(V, 2, dtype=torch.float32, device=dev))
+    side = torch.empty(V, dtype=torch.uint8, device=dev)
+    _check(lib.nerfart_mc_emit_edges(ptr, *dims, float(level), _dev(ws, torch.uint8, "ws"), ws.numel(), edge.data_ptr(), bracket.data_ptr(), t.data_ptr(),
+                                     best.data_ptr(), side.data_ptr(), V, _stream()), "nerfart_mc_emit_edges")
+    return edge, bracket, t, best, side
+
+
+def mesh_edge_points(edge, t, dims, origin, spacing, out=None):
+    """nerfart_mesh_edge_points: pts [V, 3] float32 = the vertices at parameter t [V] on their grid edges edge [V] (int32) of a volume of
+    dims = (nx, ny, nz), in the frame origin / spacing - mc_emit's arithmetic.  out: a caller's [V, 3] buffer (a vertex whose edge is not one of
+    the volume's keeps its row), else a fresh, zeroed one."""
+    V = edge.shape[0]
+    if t.shape != (V,):
+        raise NerfartHipError(f"t must be [{V}] (got {tuple(t.shape)})")
+    if out is None:
+        out = torch.zeros(V, 3, dtype=torch.float32, device=edge.device)
+    elif tuple(out.shape) != (V, 3):
+        raise NerfartHipError(f"out must be [{V}, 3] (got {tuple(out.shape)})")
+    o, s = (C.c_float * 3)(*[float(x) for x in origin]), (C.c_float * 3)(*[float(x) for x in spacing])
+    nx, ny, nz = (int(d) for d in dims)
+    _check(lib.nerfart_mesh_edge_points(_dev(edge, torch.int32, "edge"), _dev(t, name="t"), V, nx, ny, nz, C.cast(o, C.c_void_p), C.cast(s, C.c_void_p),
+                                        _dev(out, name="out"), _stream()), "nerfart_mesh_edge_points")
+    return out
+
+
+def mesh_edge_refine_step(f, level: float, bracket, t, best, side):
+    """nerfart_mesh_edge_refine_step, in place on (bracket [V, 4], t [V], best [V, 2], side [V] uint8): one step of bracket-keeping false position
+    (Illinois) given f [V] = the SDF at the points of the current t."""
+    V = t.shape[0]
+    if f.shape != (V,) or tuple(bracket.shape) != (V, 4) or tuple(best.shape) != (V, 2) or side.shape != (V,):
+        raise NerfartHipError(f"mesh_edge_refine_step: f [{V}], bracket [{V}, 4], best [{V}, 2], side [{V}] expected "
+                              f"(got {tuple(f.shape)}, {tuple(bracket.shape)}, {tuple(best.shape)}, {tuple(side.shape)})")
+    _check(lib.nerfart_mesh_edge_refine_step(_dev(f, name="f"), float(level), V, _dev(bracket, name="bracket"), _dev(t, name="t"), _dev(best, name="best"),
+                                             _dev(side, torch.uint8, "side"), _stream()), "nerfart_mesh_edge_refine_step")
 
 
 def nabla_workspace(precision: int, device):

@@ -4,7 +4,8 @@ the GPU (nerfart_amd.mesh_util.extract_mesh: the SDF kernel, csrc/marching_cubes
 
     python tools/extract_surface.py --config configs/volsdf.yaml --load_pt ckpts/latest.pt --N 512 --volume_size 2.0 --out surface.ply
 
-Without --load_pt the mesh is the model's sphere initialisation.  `--k1:k2 v` overrides of the config work as everywhere (nerfart_amd.config)."""
+`--refine 5 --normals --colors` (no reference counterpart) moves the vertices onto the surface along their grid edges and adds per-vertex normals and
+colours to the file; without them the file is the reference's two elements.  Without --load_pt the mesh is the model's sphere initialisation.  `--k1:k2 v` overrides of the config work as everywhere (nerfart_amd.config)."""
 import os
 import sys
 
@@ -24,6 +25,10 @@ def parse(argv=None):
     parser.add_argument("--level", type=float, default=0.0)
     parser.add_argument("--chunk", type=int, default=1 << 24, help="grid points per SDF launch")
     parser.add_argument("--out", type=str, default="surface.ply")
+    parser.add_argument("--refine", type=int, default=0, help="SDF evaluations per vertex moving it along its grid edge onto the surface (0: the "
+                                                              "interpolated vertices, the reference's; 5 is plenty)")
+    parser.add_argument("--normals", action="store_true", help="write nx ny nz: the normalised SDF gradient at every vertex")
+    parser.add_argument("--colors", action="store_true", help="write red green blue: the radiance net's colour looking down the normal")
     args, unknown = parser.parse_known_args(argv)
     return args, cfg.load_config(args, unknown)
 
@@ -38,7 +43,8 @@ def main():
         state = torch.load(args.load_pt, map_location="cpu")
         model.load_state_dict(state["model"] if "model" in state else state)
     model.to(dev)
-    path = mesh_util.extract_mesh(model.implicit_surface, volume_size=args.volume_size, level=args.level, N=args.N, filepath=args.out, chunk=args.chunk)
+    path = mesh_util.extract_mesh(model.implicit_surface, volume_size=args.volume_size, level=args.level, N=args.N, filepath=args.out, chunk=args.chunk,
+                                  refine_evals=args.refine, vertex_normals=args.normals, color_model=model if args.colors else None)
     print(path)
 
 
