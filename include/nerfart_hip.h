@@ -441,6 +441,37 @@ int nerfart_mesh_edge_points(const unsigned* edge, const float* t, unsigned V, i
                              float* pts_out, void* stream);
 int nerfart_mesh_edge_refine_step(const float* f, float level, unsigned V, float* bracket, float* t, float* best, unsigned char* side, void* stream);
 
+/* ---- connected components of an indexed mesh and the compaction that drops some of them (csrc/mesh_components.hip;
+ * mesh_util.mesh_components / filter_components, extract_mesh(keep_largest=, min_component_faces=): the floaters of a fine-tuned field are removed
+ * without the mesh leaving the GPU).  Additions to ABI 5; no counterpart in the reference.  faces [F, 3] int32 indexes V vertices - nerfart_mc_emit's
+ * mesh is indexed, one vertex per grid edge, so nothing has to be welded.  Everything is integers: the results below are defined uniquely.
+ *   THE RULE: two vertices are connected when a face contains both, and components are the classes of the transitive closure - VERTEX
+ *     connectivity: two triangles that share a single vertex are one component.  A vertex in no face is a component of its own.  A face with an
+ *     index outside [0, V) is BAD: it joins nothing, is counted nowhere, never survives a compaction, and nothing is read or written outside the
+ *     arrays because of it.
+ *   nerfart_mesh_components: label [V] int32, label[v] = the smallest vertex index of v's component;  n_faces [V] uint32, n_faces[r] = the number
+ *     of (good) faces of the component whose label is r, 0 at every index that is not a label;  info [3] uint32 (DEVICE) = {components, components
+ *     with at least one face, 1 if any face is bad}.  Asynchronous, no host read inside.  V == 0 zeroes info and launches nothing; F == 0 labels
+ *     every vertex with itself.  (A lock-free union-find that links the larger root under the smaller, so parent[v] <= v throughout: the
+ *     smallest index of a component is the one root left, whatever the order of work - csrc/mesh_components.hip.)
+ *   nerfart_mesh_compact_workspace_bytes: the size of the caller's workspace for the two calls below (the scanned (vertex, face) offsets of
+ *     max(V, F, 1) items plus their block sums; 0 = bad sizes, see nerfart_last_error).
+ *   nerfart_mesh_compact_count: keep [V] uint8 is indexed BY LABEL: component r survives iff keep[r] != 0.  Vertex v survives iff
+ *     keep[label[v]]; face f survives iff it is good and keep[label[faces[f][0]]] (a label outside [0, V) survives nothing).  Fills the workspace
+ *     and counts [2] (DEVICE, 8-byte aligned) = {V' surviving vertices, F' surviving faces}.  Asynchronous.
+ *   nerfart_mesh_compact_emit: from the SAME, untouched workspace: src_vertex [V'] int32 = the old indices of the surviving vertices, ascending
+ *     (so new vertex i is old vertex src_vertex[i]: any per-vertex array is gathered with it);  faces_out [F', 3] int32 = the surviving faces in
+ *     their old order, every index replaced by the number of surviving vertices before it.  V_out and F_out are the sizes of the caller's arrays
+ *     (every write is checked against them); both 0 launches nothing.  No atomics: two runs give the same bits.
+ * Refused with 2 before any launch: a null pointer (of an array that is not empty), V or F >= 2^31, 3 F >= 2^32, counts not 8-byte aligned, a
+ * workspace smaller than the query's answer (or not 16-byte aligned). */
+int nerfart_mesh_components(const int* faces, unsigned F, unsigned V, int* label, unsigned* n_faces, unsigned* info, void* stream);
+size_t nerfart_mesh_compact_workspace_bytes(unsigned V, unsigned F);
+int nerfart_mesh_compact_count(const int* label, const unsigned char* keep, const int* faces, unsigned V, unsigned F, void* ws, size_t ws_bytes,
+                               unsigned* counts, void* stream);
+int nerfart_mesh_compact_emit(const int* label, const unsigned char* keep, const int* faces, unsigned V, unsigned F, const void* ws, size_t ws_bytes,
+                              int* src_vertex, int* faces_out, unsigned V_out, unsigned F_out, void* stream);
+
 /* ---- VGG16 perceptual term (criteria/perp_loss.py:9-57): torchvision vgg16.features[:16] (through relu3_3) as
  * implicit-GEMM 3 x 3 convolutions on v_mfma_f32_32x32x2_f32 (fp32 operands as the reference's net; csrc/vgg_conv.hip), L1
  * between prediction and target features.

@@ -6,14 +6,15 @@
 //   k_mc_classify  one thread per grid point, lanes along z: byte 1 = which owned edges change sign (bit axis), byte 2 = the case index of the
 //                  cell whose origin the point is (0 for the points of the last layers, which are no cell origin); a flag for non-finite values.
 //   k_mc_scan      exclusive scan of (vertices per point 0..3, triangles per cell) over all points in linear order: per 512-item block
-//                  (wave64 shuffles + LDS) with block sums, the same kernel on the block sums until one block is left, k_mc_add_back on the
-//                  way down.  Every kernel runs to completion on its own: no workgroup ever waits for another.
+//                  (wave64 shuffles + LDS) with block sums, the same scan on the block sums until one block is left, an add-back on the
+//                  way down (csrc/pair_scan.h, shared with csrc/mesh_components.hip).  Every kernel runs to completion on its own: no
+//                  workgroup ever waits for another.
 //   k_mc_emit      a point writes its vertices at its scanned offset in axis order; a cell writes its triangles at its scanned offset in table
 //                  order, a vertex index being the owner's scanned offset + the rank of the edge among the owner's flagged edges.  No atomics:
 //                  the output is a pure function of the volume, so two runs are bit-identical.  Every write is checked against V / F.
 //   k_mc_emit_edges  the same walk, writing per vertex which grid edge it sits on and the initial state of the vertex refinement
 //                  (csrc/mesh_vertices.hip) instead of a position.
-#include "host_util.h"
+#include "pair_scan.h"
 #include <cmath>
 #include <string>
 #define MC_TABLE_DECL static __device__ const
@@ -21,19 +22,15 @@
 
 namespace nerfart {
 
-constexpr int MC_SCAN_BLOCK = 512;       // items per scan block: 256 threads x 2 (tests/test_gpu_marching_cubes.py states it)
 constexpr int MC_TILE_Z = 64, MC_TILE_Y = 4;       // a 256-thread block covers 64 points along z (one wave = one coalesced row) x 4 rows
 constexpr int MC_X_CHUNK = 8;            // ... and, in k_mc_classify, 8 slabs along x, carrying the shared slab in registers
-constexpr int MC_MAX_LEVELS = 4;         // 3 n < 2^31 points / 512^3 < 8: at most three block-sum levels live in the workspace
 
 // the workspace, carved in this order (each buffer rounded up to 256 bytes): flags [n] bytes, cases [n] bytes, off [n][2] (vertex offset,
 // triangle offset), then per block-sum level k its [m_k][2] sums, m_0 = ceil(n / 512), m_{k+1} = ceil(m_k / 512), while m_k > 1
 struct McWorkspace {
     unsigned char *flags, *cases;
     unsigned* off;
-    unsigned* lvl[MC_MAX_LEVELS];
-    unsigned lvl_m[MC_MAX_LEVELS];
-    int n_lvl;
+    PairScanLevels lvl;
     size_t bytes;
 };
 static McWorkspace mc_carve(void* base, size_t n) {
@@ -42,10 +39,7 @@ static McWorkspace mc_carve(void* base, size_t n) {
     w.flags = c.take<unsigned char>(n);
     w.cases = c.take<unsigned char>(n);
     w.off = c.take<unsigned>(2 * n);
-    for (size_t m = (n + MC_SCAN_BLOCK - 1) / MC_SCAN_BLOCK; m > 1 && w.n_lvl < MC_MAX_LEVELS; m = (m + MC_SCAN_BLOCK - 1) / MC_SCAN_BLOCK) {
-        w.lvl[w.n_lvl] = c.take<unsigned>(2 * m);
-        w.lvl_m[w.n_lvl++] = (unsigned)m;
-    }
+    pair_scan_carve(c, n, w.lvl);
     w.bytes = c.off;
     return w;
 }
@@ -98,49 +92,10 @@ __global__ void __launch_bounds__(256) k_mc_classify(const float* __restrict__ v
     if (bad) *nonfinite = 1u;
 }
 
-// One 512-item block of the exclusive scan of pairs: arr[i] = (sum of v before i, sum of t before i) within the block, sums[block] = the block's
-// totals.  FROM_BYTES: the items are (vertices of point i, triangles of cell i) read from the classify bytes; else arr itself (block sums).
-template <bool FROM_BYTES>
-__global__ void __launch_bounds__(256) k_mc_scan(const unsigned char* __restrict__ flags, const unsigned char* __restrict__ cases, uint2* __restrict__ arr,
-                                                 unsigned m, uint2* __restrict__ sums) {
-    __shared__ unsigned wave_tot[4][2];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const size_t i0 = (size_t)blockIdx.x * MC_SCAN_BLOCK + 2 * threadIdx.x;
-    unsigned v[2] = {0, 0}, t[2] = {0, 0};
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        if (i0 + k < m) {
-            if (FROM_BYTES) { v[k] = __popc(flags[i0 + k] & 7u); t[k] = mc_tri_count[cases[i0 + k]]; }
-            else { const uint2 a = arr[i0 + k]; v[k] = a.x; t[k] = a.y; }
-        }
-    }
-    const unsigned sv = v[0] + v[1], st = t[0] + t[1];
-    unsigned iv = sv, it = st;                       // inclusive over the wave
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned a = __shfl_up(iv, d, 64), b = __shfl_up(it, d, 64);
-        if (lane >= d) { iv += a; it += b; }
-    }
-    if (lane == 63) { wave_tot[w][0] = iv; wave_tot[w][1] = it; }
-    __syncthreads();
-    unsigned ev = iv - sv, et = it - st;             // exclusive at this thread's first item
-    for (int j = 0; j < w; ++j) { ev += wave_tot[j][0]; et += wave_tot[j][1]; }
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        if (i0 + k < m) arr[i0 + k] = make_uint2(ev, et);
-        ev += v[k]; et += t[k];
-    }
-    if (threadIdx.x == 255) sums[blockIdx.x] = make_uint2(ev, et);
-}
-
-// arr[i] += sums[i / 512] (sums already scanned: the offset of the block)
-__global__ void __launch_bounds__(256) k_mc_add_back(uint2* __restrict__ arr, unsigned m, const uint2* __restrict__ sums) {
-    const uint2 s = sums[blockIdx.x];
-    const size_t i0 = (size_t)blockIdx.x * MC_SCAN_BLOCK + 2 * threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        if (i0 + k < m) { uint2 a = arr[i0 + k]; a.x += s.x; a.y += s.y; arr[i0 + k] = a; }
-    }
+// The first level of the scan (csrc/pair_scan.h): the items are (vertices of point i, triangles of cell i) read from the classify bytes.
+__global__ void __launch_bounds__(256) k_mc_scan(const unsigned char* __restrict__ flags, const unsigned char* __restrict__ cases, uint2* __restrict__ off,
+                                                 unsigned n, uint2* __restrict__ sums) {
+    pair_scan_block([&](size_t i) { return make_uint2(__popc(flags[i] & 7u), mc_tri_count[cases[i]]); }, off, n, sums);
 }
 
 struct McFrame { float o[3], s[3]; };
@@ -289,22 +244,10 @@ int nerfart_mc_count(const float* vol, int nx, int ny, int nz, float level, void
     const int by = (ny + MC_TILE_Y - 1) / MC_TILE_Y, bz = (nz + MC_TILE_Z - 1) / MC_TILE_Z, bx = (nx + MC_X_CHUNK - 1) / MC_X_CHUNK;
     hipLaunchKernelGGL(k_mc_classify, dim3((unsigned)((size_t)bx * by * bz)), dim3(256), 0, st, vol, nx, ny, nz, level, by, bz, w.flags, w.cases, counts + 2);
     NERFART_HIP(hipGetLastError());
-    // up: each level's block sums are the next level's items; the last level is one block, whose sums are the totals (V, F)
-    auto blocks = [](unsigned m) { return dim3((m + MC_SCAN_BLOCK - 1) / MC_SCAN_BLOCK); };
-    auto sums_of = [&](int k) { return (uint2*)(k < w.n_lvl ? w.lvl[k] : counts); };      // sums of level k - 1 (k = 0: of the points)
-    hipLaunchKernelGGL(k_mc_scan<true>, blocks((unsigned)n), dim3(256), 0, st, w.flags, w.cases, (uint2*)w.off, (unsigned)n, sums_of(0));
+    hipLaunchKernelGGL(k_mc_scan, pair_scan_blocks((unsigned)n), dim3(256), 0, st, w.flags, w.cases, (uint2*)w.off, (unsigned)n,
+                       pair_scan_sums(w.lvl, 0, counts));
     NERFART_HIP(hipGetLastError());
-    for (int k = 0; k < w.n_lvl; ++k) {
-        hipLaunchKernelGGL(k_mc_scan<false>, blocks(w.lvl_m[k]), dim3(256), 0, st, nullptr, nullptr, (uint2*)w.lvl[k], w.lvl_m[k], sums_of(k + 1));
-        NERFART_HIP(hipGetLastError());
-    }
-    // down: level k is complete once level k + 1 has been added to it
-    for (int k = w.n_lvl - 1; k >= 0; --k) {
-        uint2* below = (uint2*)(k ? w.lvl[k - 1] : w.off);
-        const unsigned m = k ? w.lvl_m[k - 1] : (unsigned)n;
-        hipLaunchKernelGGL(k_mc_add_back, blocks(m), dim3(256), 0, st, below, m, (const uint2*)w.lvl[k]);
-        NERFART_HIP(hipGetLastError());
-    }
+    if (int rc = pair_scan_finish(w.off, (unsigned)n, w.lvl, counts, st)) return rc;      // the totals (V, F) land in counts[0..1]
     return 0;
 }
 

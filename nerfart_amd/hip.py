@@ -136,6 +136,10 @@ _SIGS = {
     "nerfart_mc_emit_edges": (_i, [_p, _i, _i, _i, _f, _p, _ll, _p, _p, _p, _p, _p, _i, _p]),
     "nerfart_mesh_edge_points": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p]),
     "nerfart_mesh_edge_refine_step": (_i, [_p, _f, _i, _p, _p, _p, _p, _p]),
+    "nerfart_mesh_components": (_i, [_p, _i, _i, _p, _p, _p, _p]),
+    "nerfart_mesh_compact_workspace_bytes": (_ll, [_i, _i]),
+    "nerfart_mesh_compact_count": (_i, [_p, _p, _p, _i, _i, _p, _ll, _p, _p]),
+    "nerfart_mesh_compact_emit": (_i, [_p, _p, _p, _i, _i, _p, _ll, _p, _p, _i, _i, _p]),
     "nerfart_pack_surface_blob": (_i, [_i, _i, _p, _p, _p, _p, _ll, _p, _ll, _p]),
     "nerfart_pack_radiance_blob": (_i, [_i, _i, _p, _p, _p, _p, _p, _p, _p, _ll, _p, _ll, _p]),
     "nerfart_pack_plan_debug": (_i, [_i, _i, _i] + [_p] * 6),
@@ -387,6 +391,74 @@ def mesh_edge_refine_step(f, level: float, bracket, t, best, side):
                               f"(got {tuple(f.shape)}, {tuple(bracket.shape)}, {tuple(best.shape)}, {tuple(side.shape)})")
     _check(lib.nerfart_mesh_edge_refine_step(_dev(f, name="f"), float(level), V, _dev(bracket, name="bracket"), _dev(t, name="t"), _dev(best, name="best"),
                                              _dev(side, torch.uint8, "side"), _stream()), "nerfart_mesh_edge_refine_step")
+
+
+def _mesh_faces(faces, V: int):
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise NerfartHipError(f"faces must be [F, 3] (got {tuple(faces.shape)})")
+    if V < 0:
+        raise NerfartHipError(f"the vertex count must be >= 0 (got {V})")
+    return _dev(faces, torch.int32, "faces"), int(faces.shape[0])
+
+
+def mesh_components(faces, V: int):
+    """nerfart_mesh_components on faces [F, 3] (int32) over V vertices: (label [V] int32 - the smallest vertex index of the vertex's component -,
+    n_faces [V] int32 - at a label the component's face count, 0 elsewhere -, info [3] int32 = (components, components with a face, 1 if a face
+    holds an index outside [0, V))), all on faces' device.  No host synchronisation."""
+    V = int(V)
+    ptr, F = _mesh_faces(faces, V)
+    label = torch.empty(V, dtype=torch.int32, device=faces.device)
+    n_faces = torch.empty(V, dtype=torch.int32, device=faces.device)
+    info = torch.empty(3, dtype=torch.int32, device=faces.device)
+    _check(lib.nerfart_mesh_components(ptr, F, V, label.data_ptr(), n_faces.data_ptr(), _dev(info, torch.int32, "info"), _stream()),
+           "nerfart_mesh_components")
+    return label, n_faces, info
+
+
+def mesh_compact_workspace_bytes(V: int, F: int) -> int:
+    """nerfart_mesh_compact_workspace_bytes; bad sizes (V or F >= 2^31, 3 F >= 2^32) raise with the library's message."""
+    n = int(lib.nerfart_mesh_compact_workspace_bytes(V, F))
+    _check(0 if n else 2, "nerfart_mesh_compact_workspace_bytes")
+    return n
+
+
+def _mesh_compact_args(label, keep, faces, V: int):
+    V = int(V)
+    ptr, F = _mesh_faces(faces, V)
+    if label.shape != (V,) or keep.shape != (V,):
+        raise NerfartHipError(f"label and keep must be [{V}] (got {tuple(label.shape)}, {tuple(keep.shape)})")
+    return _dev(label, torch.int32, "label"), _dev(keep, torch.uint8, "keep"), ptr, V, F
+
+
+def mesh_compact_count(label, keep, faces, V: int, ws=None):
+    """nerfart_mesh_compact_count: (ws, counts) - the filled workspace (uint8; a caller's own, or a fresh one: it must stay untouched until
+    mesh_compact_emit has run) and the int32 device tensor counts [2] = (surviving vertices, surviving faces).  keep [V] uint8 is indexed by
+    label.  No host synchronisation."""
+    lp, kp, fp, V, F = _mesh_compact_args(label, keep, faces, V)
+    if ws is None:
+        ws = torch.empty(mesh_compact_workspace_bytes(V, F), dtype=torch.uint8, device=faces.device)
+    counts = torch.empty(2, dtype=torch.int32, device=faces.device)
+    _check(lib.nerfart_mesh_compact_count(lp, kp, fp, V, F, _dev(ws, torch.uint8, "ws"), ws.numel(), counts.data_ptr(), _stream()),
+           "nerfart_mesh_compact_count")
+    return ws, counts
+
+
+def mesh_compact_emit(label, keep, faces, V: int, ws, V_out: int, F_out: int):
+    """nerfart_mesh_compact_emit: (src_vertex [V_out] int32 - the old indices of the surviving vertices, ascending -, faces_out [F_out, 3] int32 -
+    the surviving faces in their old order, renumbered) from the workspace mesh_compact_count filled for the same arrays."""
+    lp, kp, fp, V, F = _mesh_compact_args(label, keep, faces, V)
+    src = torch.empty(int(V_out), dtype=torch.int32, device=faces.device)
+    out = torch.empty(int(F_out), 3, dtype=torch.int32, device=faces.device)
+    _check(lib.nerfart_mesh_compact_emit(lp, kp, fp, V, F, _dev(ws, torch.uint8, "ws"), ws.numel(), src.data_ptr(), out.data_ptr(), int(V_out), int(F_out),
+                                         _stream()), "nerfart_mesh_compact_emit")
+    return src, out
+
+
+def mesh_compact(label, keep, faces, V: int):
+    """mesh_compact_count, ONE host read (the two sizes), mesh_compact_emit: (src_vertex [V'], faces_out [F', 3])."""
+    ws, counts = mesh_compact_count(label, keep, faces, V)
+    V_out, F_out = (int(c) for c in counts.cpu())
+    return mesh_compact_emit(label, keep, faces, V, ws, V_out, F_out)
 
 
 def nabla_workspace(precision: int, device):

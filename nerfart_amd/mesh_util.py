@@ -18,6 +18,8 @@ scikit-image and plyfile, for machines that have them.
 Beyond the reference, off by default: `extract_mesh(refine_evals=, vertex_normals=, color_model=)` keeps every vertex as (grid edge, t) and moves t
 against the SDF without leaving the edge (`refine_vertices`; csrc/mesh_vertices.hip), and writes per-vertex normals (the SDF gradient) and
 colours (the radiance net looking down the normal; `vertex_attributes`) as extra PLY vertex properties.
+`extract_mesh(keep_largest=, min_component_faces=)` drops the floaters: `mesh_components` labels the connected components of the indexed mesh
+on the GPU (csrc/mesh_components.hip), `filter_components` keeps the largest ones and compacts vertices and faces.
 """
 import numpy as np
 import torch
@@ -112,6 +114,46 @@ def vertex_attributes(model, pts):
     return hip.normalize_dirs(nabla.contiguous()), quantize_colors(rgb)
 
 
+def mesh_components(faces, n_verts: int):
+    """Connected components of the indexed mesh faces [F, 3] (int32, on the GPU) over n_verts vertices (csrc/mesh_components.hip; two vertices
+    are connected when a face contains both, so triangles sharing one vertex are one component; a vertex in no face is its own):
+    (label [V] int32 - the smallest vertex index of the vertex's component -, roots [C] int32 - the labels in RANK order: face count descending,
+    ties broken by the smaller label -, n_faces [C] int32 - the face counts in that order), all on faces' device.  One host read (the flag);
+    a face with an index outside [0, n_verts) raises ValueError.  CPU tensors are refused: there is no CPU path."""
+    from . import hip
+    label, n_faces, info = hip.mesh_components(faces, n_verts)
+    if int(info.cpu()[2]):
+        raise ValueError(f"mesh_components: a face holds a vertex index outside [0, {int(n_verts)})")
+    roots = torch.nonzero(label == torch.arange(int(n_verts), dtype=torch.int32, device=label.device)).reshape(-1)      # ascending
+    count, order = torch.sort(n_faces[roots], stable=True, descending=True)           # stable over ascending roots: ties keep the smaller label first
+    return label, roots[order].to(torch.int32), count
+
+
+def filter_components(verts, faces, keep_largest=None, min_faces=None):
+    """Drops connected components of the mesh (verts [V, ...], faces [F, 3] int32, on the GPU): a component survives iff
+    (keep_largest is None or its rank < keep_largest) and (min_faces is None or its face count >= min_faces), rank as mesh_components orders
+    them.  Returns (verts', faces', src_vertex): the surviving vertices and faces in their old order, faces renumbered, and src_vertex [V'] int32
+    with verts' = verts[src_vertex] - any other per-vertex array is gathered with it.  Nothing surviving gives (0, ...) tensors."""
+    from . import hip
+    if keep_largest is None and min_faces is None:
+        raise ValueError("filter_components: give keep_largest and / or min_faces")
+    if keep_largest is not None and keep_largest < 1:
+        raise ValueError(f"filter_components: keep_largest must be >= 1 (got {keep_largest})")
+    if min_faces is not None and min_faces < 1:
+        raise ValueError(f"filter_components: min_faces must be >= 1 (got {min_faces})")
+    V = int(verts.shape[0])
+    label, roots, count = mesh_components(faces, V)
+    survives = torch.ones_like(roots, dtype=torch.bool)
+    if keep_largest is not None:
+        survives &= torch.arange(roots.shape[0], device=roots.device) < int(keep_largest)
+    if min_faces is not None:
+        survives &= count >= int(min_faces)
+    keep = torch.zeros(V, dtype=torch.uint8, device=faces.device)
+    keep[roots[survives].long()] = 1
+    src_vertex, faces_out = hip.mesh_compact(label, keep, faces, V)
+    return verts[src_vertex.long()], faces_out, src_vertex
+
+
 def write_ply(path, verts, faces, normals=None, colors=None):
     """Binary little-endian PLY: `element vertex` with float x, y, z and `element face` with `property list uchar int vertex_indices` - the file
     plyfile writes for the reference's two elements (mesh_util.py:57-80).  verts [V, 3], faces [F, 3]: tensors or arrays.  Optional per-vertex
@@ -151,9 +193,11 @@ def write_ply(path, verts, faces, normals=None, colors=None):
 
 
 @torch.no_grad()
-def _extract_mesh_with_vertex_data(implicit_surface, volume_size, level, N, filepath, chunk, refine_evals, vertex_normals, color_model):
+def _extract_mesh_with_vertex_data(implicit_surface, volume_size, level, N, filepath, chunk, refine_evals, vertex_normals, color_model,
+                                   keep_largest=None, min_component_faces=None):
     """extract_mesh with any of refine_evals / vertex_normals / color_model set: every vertex is (edge, t); positions are written in the placement
-    frame, every network query is made in the model's frame, so the refinement does not depend on how the mesh is placed."""
+    frame, every network query is made in the model's frame, so the refinement does not depend on how the mesh is placed.  Components are
+    dropped once, at the end, from positions, faces, normals and colours together."""
     from . import hip
     if refine_evals < 0:
         raise ValueError(f"extract_mesh: refine_evals must be >= 0 (got {refine_evals})")
@@ -176,11 +220,15 @@ def _extract_mesh_with_vertex_data(implicit_surface, volume_size, level, N, file
             normals, colors = vertex_attributes(color_model, pts)
         else:
             normals = hip.normalize_dirs(implicit_surface.forward_with_nablas(pts)[1].contiguous()) if V else pts
+    if keep_largest is not None or min_component_faces is not None:
+        verts, faces, src = filter_components(verts, faces, keep_largest, min_component_faces)
+        normals, colors = (a if a is None else a[src.long()] for a in (normals, colors))
     return write_ply(filepath, verts, faces, normals if vertex_normals else None, colors)
 
 
 def extract_mesh(implicit_surface, volume_size=2.0, level=0.0, N=512, filepath="./surface.ply", show_progress=True, chunk=1 << 24,
-                 reference_shear: bool = False, backend: str = "native", refine_evals: int = 0, vertex_normals: bool = False, color_model=None):
+                 reference_shear: bool = False, backend: str = "native", refine_evals: int = 0, vertex_normals: bool = False, color_model=None,
+                 keep_largest: int = None, min_component_faces: int = None):
     """mesh_util.extract_mesh: SDF volume -> marching cubes -> .ply.  backend="native" (default): marching_cubes + write_ply above, nothing
     third-party, the volume stays on the GPU; backend="skimage": the reference's route (needs scikit-image and plyfile).  Both place the mesh as
     the reference does: spacing volume_size / N, offset -volume_size / 2 (mesh_util.py:112).  reference_shear=True samples
@@ -191,15 +239,25 @@ def extract_mesh(implicit_surface, volume_size=2.0, level=0.0, N=512, filepath="
     Three options without a reference counterpart (native backend, regular grid; all at their defaults: the path above, untouched):
     refine_evals >= 1 moves every vertex along its grid edge to the best of that many SDF evaluations (refine_vertices; 1 = the interpolated
     vertex), vertex_normals writes nx ny nz = the normalised SDF gradient, color_model (the whole VolSDF / NeuS model) writes red green blue =
-    its radiance looking down the normal (vertex_attributes).  Faces are marching_cubes' own, unchanged."""
+    its radiance looking down the normal (vertex_attributes).  Faces are marching_cubes' own, unchanged.
+
+    keep_largest / min_component_faces (native backend, the sheared grid included; both None: the paths above, untouched) drop the floaters
+    before the file is written: only the keep_largest largest connected components, and / or only those of at least min_component_faces faces,
+    survive (filter_components; csrc/mesh_components.hip), with their vertices, normals and colours."""
+    filtering = keep_largest is not None or min_component_faces is not None
+    if filtering and backend != "native":
+        raise ValueError("extract_mesh: keep_largest / min_component_faces need backend='native' (the components are found on the GPU)")
     if refine_evals or vertex_normals or color_model is not None:
         if reference_shear or backend != "native":
             raise ValueError("extract_mesh: refine_evals / vertex_normals / color_model need backend='native' and the regular grid "
                              "(the sheared grid has no regular frame, scikit-image gives no edge table)")
-        return _extract_mesh_with_vertex_data(implicit_surface, volume_size, level, N, filepath, chunk, int(refine_evals), vertex_normals, color_model)
+        return _extract_mesh_with_vertex_data(implicit_surface, volume_size, level, N, filepath, chunk, int(refine_evals), vertex_normals, color_model,
+                                              keep_largest, min_component_faces)
     if backend == "native":
         vol = sdf_volume(implicit_surface, volume_size, N, chunk, reference_shear=reference_shear)
         verts, faces = marching_cubes(vol, level=level, spacing=[volume_size / N] * 3, origin=[-volume_size / 2.0] * 3)
+        if filtering:
+            verts, faces, _ = filter_components(verts, faces, keep_largest, min_component_faces)
         return write_ply(filepath, verts, faces)
     if backend != "skimage":
         raise ValueError(f"extract_mesh: backend must be 'native' or 'skimage' (got {backend!r})")

@@ -5,7 +5,8 @@ the GPU (nerfart_amd.mesh_util.extract_mesh: the SDF kernel, csrc/marching_cubes
     python tools/extract_surface.py --config configs/volsdf.yaml --load_pt ckpts/latest.pt --N 512 --volume_size 2.0 --out surface.ply
 
 `--refine 5 --normals --colors` (no reference counterpart) moves the vertices onto the surface along their grid edges and adds per-vertex normals and
-colours to the file; without them the file is the reference's two elements.  Without --load_pt the mesh is the model's sphere initialisation.  `--k1:k2 v` overrides of the config work as everywhere (nerfart_amd.config)."""
+colours to the file; without them the file is the reference's two elements.  `--keep_largest 1` (or `--min_faces M`) drops the floaters: only the
+largest connected components of the surface are written.  Without --load_pt the mesh is the model's sphere initialisation.  `--k1:k2 v` overrides of the config work as everywhere (nerfart_amd.config)."""
 import os
 import sys
 
@@ -29,6 +30,9 @@ def parse(argv=None):
                                                               "interpolated vertices, the reference's; 5 is plenty)")
     parser.add_argument("--normals", action="store_true", help="write nx ny nz: the normalised SDF gradient at every vertex")
     parser.add_argument("--colors", action="store_true", help="write red green blue: the radiance net's colour looking down the normal")
+    parser.add_argument("--keep_largest", type=int, default=None, help="keep only the K largest connected components of the mesh (by faces): "
+                                                                       "drops the floaters")
+    parser.add_argument("--min_faces", type=int, default=None, help="keep only the connected components of at least M faces")
     args, unknown = parser.parse_known_args(argv)
     return args, cfg.load_config(args, unknown)
 
@@ -44,7 +48,8 @@ def main():
         model.load_state_dict(state["model"] if "model" in state else state)
     model.to(dev)
     path = mesh_util.extract_mesh(model.implicit_surface, volume_size=args.volume_size, level=args.level, N=args.N, filepath=args.out, chunk=args.chunk,
-                                  refine_evals=args.refine, vertex_normals=args.normals, color_model=model if args.colors else None)
+                                  refine_evals=args.refine, vertex_normals=args.normals, color_model=model if args.colors else None,
+                                  keep_largest=args.keep_largest, min_component_faces=args.min_faces)
     print(path)
 
 
