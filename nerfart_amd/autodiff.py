@@ -164,6 +164,21 @@ def _eikonal_terms(nab, R: int, P: int, w_eikonal: float, group_rays):
     return eik, (coef * err / nn_)[:, None] * nab
 
 
+def _native_backward(model, who: str, device, accum, call):
+    """What the ray-level backward wrappers share around their ONE library call `call(raw)`: the precision check, the step's accumulator
+    (None: one of this call's own, flushed into .grad here) and the eikonal loss the call added to the raw buffer's scalar (0-d)."""
+    from . import hip
+    _need_split_bf16(model, who)
+    acc = accum if accum is not None else GradAccumulator()
+    raw = acc.buffer(device)
+    before = acc._scalar(hip.RAW_EIKONAL).clone()
+    call(raw)
+    eik = acc._scalar(hip.RAW_EIKONAL) - before
+    if accum is None:
+        acc.flush(model)
+    return eik
+
+
 def volsdf_backward_samples_native(model, rays_o, rays_d, d_all, g_rgb, w_eikonal=0.1, use_eikonal=True, white_bkgd=False, ab=None,
                                    nbar_extra=None, accum=None, state=None, eik_group_rays=None, g_acc=None):
     """Pass 2 of the fine-tune step for one launch group of rays: ONE call of nerfart_volsdf_render_bwd, which accumulates into the
@@ -176,25 +191,15 @@ def volsdf_backward_samples_native(model, rays_o, rays_d, d_all, g_rgb, w_eikona
     eik_group_rays: the rays are several `eik_group_rays`-ray patches of the reference in one launch (the eikonal mean is
     per patch); the returned loss is then the SUM over those patches."""
     from . import hip
-    _need_split_bf16(model, "volsdf_backward_samples_native")
-    surf_blob, rad_blob = model.packed()
-    if ab is None:
-        alpha, beta = model.forward_ab()
-        ab = (float(alpha), float(beta))
-    acc = accum if accum is not None else GradAccumulator()
-    raw = acc.buffer(d_all.device)
-    before = acc._scalar(hip.RAW_EIKONAL).clone()
-    hip.volsdf_render_bwd(surf_blob, rad_blob, model.view_tiles, model.implicit_surface.embed_multires, rays_o.contiguous(), rays_d.contiguous(),
-                          d_all.contiguous(), g_rgb.contiguous(), raw, R_bg=model.obj_bounding_radius, alpha=ab[0], beta=ab[1],
-                          white_bkgd=white_bkgd, w_eikonal=w_eikonal if use_eikonal else 0.0, eik_group_rays=eik_group_rays or 0,
-                          train_radiance=any(p.requires_grad for p in model.radiance_net.parameters()),
-                          g_acc=None if g_acc is None else g_acc.contiguous(),
-                          g_n_extra=None if nbar_extra is None else nbar_extra.reshape(-1, 3).contiguous(),
-                          state=None if state is None else tuple(t.contiguous() for t in state))
-    eik = acc._scalar(hip.RAW_EIKONAL) - before
-    if accum is None:
-        acc.flush(model)
-    return eik
+    def call(raw):
+        alpha, beta = ab if ab is not None else (float(x.detach()) for x in model.forward_ab())
+        hip.volsdf_render_bwd(*model.packed(), model.view_tiles, model.implicit_surface.embed_multires, rays_o.contiguous(), rays_d.contiguous(),
+                              d_all.contiguous(), g_rgb.contiguous(), raw, R_bg=model.obj_bounding_radius, alpha=alpha, beta=beta,
+                              white_bkgd=white_bkgd, w_eikonal=w_eikonal if use_eikonal else 0.0, eik_group_rays=eik_group_rays or 0,
+                              train_radiance=any(p.requires_grad for p in model.radiance_net.parameters()), g_acc=None if g_acc is None else g_acc.contiguous(),
+                              g_n_extra=None if nbar_extra is None else nbar_extra.reshape(-1, 3).contiguous(),
+                              state=None if state is None else tuple(t.contiguous() for t in state))
+    return _native_backward(model, "volsdf_backward_samples_native", d_all.device, accum, call)
 
 
 def neus_backward_samples_native(model, rays_o, rays_d, d_all, g_rgb, w_eikonal=0.1, use_eikonal=True, white_bkgd=False, s_val=None, accum=None,
@@ -205,22 +210,13 @@ def neus_backward_samples_native(model, rays_o, rays_d, d_all, g_rgb, w_eikonal=
     the opacity mask_volume (the mask BCE of the reconstruction objective).  state: (sdf, nablas[, ...]) at the samples kept from
     pass 1.  Returns the eikonal loss (0-d)."""
     from . import hip
-    _need_split_bf16(model, "neus_backward_samples_native")
-    surf_blob, rad_blob = model.packed()
-    if s_val is None:
-        s_val = float(model.forward_s())
-    acc = accum if accum is not None else GradAccumulator()
-    raw = acc.buffer(d_all.device)
-    before = acc._scalar(hip.RAW_EIKONAL).clone()
-    hip.neus_render_bwd(surf_blob, rad_blob, model.view_tiles, model.implicit_surface.embed_multires, rays_o.contiguous(), rays_d.contiguous(),
-                        d_all.contiguous(), g_rgb.contiguous(), raw, s=s_val, white_bkgd=white_bkgd, w_eikonal=w_eikonal if use_eikonal else 0.0,
-                        eik_group_rays=eik_group_rays or 0, train_radiance=any(p.requires_grad for p in model.radiance_net.parameters()),
-                        g_acc=None if g_acc is None else g_acc.contiguous(),
-                        state=None if state is None else (state[0].contiguous(), state[1].contiguous()))
-    eik = acc._scalar(hip.RAW_EIKONAL) - before
-    if accum is None:
-        acc.flush(model)
-    return eik
+    def call(raw):
+        hip.neus_render_bwd(*model.packed(), model.view_tiles, model.implicit_surface.embed_multires, rays_o.contiguous(), rays_d.contiguous(),
+                            d_all.contiguous(), g_rgb.contiguous(), raw, s=float(model.forward_s().detach()) if s_val is None else s_val,
+                            white_bkgd=white_bkgd, w_eikonal=w_eikonal if use_eikonal else 0.0, eik_group_rays=eik_group_rays or 0,
+                            train_radiance=any(p.requires_grad for p in model.radiance_net.parameters()), g_acc=None if g_acc is None else g_acc.contiguous(),
+                            state=None if state is None else (state[0].contiguous(), state[1].contiguous()))
+    return _native_backward(model, "neus_backward_samples_native", d_all.device, accum, call)
 
 
 def surface_param_backward(model, pts, nbar, sbar=None, hbar7=None, accum=None):

@@ -7,7 +7,9 @@ keys (:384-407).  upsample_algo: 'official_solution' (the one the shipped config
 from __future__ import annotations
 
 import copy
+import inspect
 from collections import OrderedDict
+from types import SimpleNamespace
 
 import torch
 import torch.nn as nn
@@ -62,6 +64,21 @@ def volume_render(rays_o, rays_d, model: NeuS, obj_bounding_radius=1.0, batched=
             v = torch.cat([p[k] for p in parts], 0) if len(parts) > 1 else parts[0][k]
             ret[k] = v.reshape(*lead, *v.shape[1:])
     return ret["rgb"], ret["depth_volume"], ret
+
+
+_ARG_DEFAULTS = {k: inspect.signature(volume_render).parameters[k].default for k in (
+    "obj_bounding_radius", "N_samples", "N_importance", "N_upsample_iters", "upsample_algo", "N_nograd_samples", "fixed_s_recp", "white_bkgd", "perturb")}
+
+
+def render_args(render_kwargs) -> SimpleNamespace:
+    """As volsdf.render_args: the arguments as THIS module's volume_render reads them (its signature's defaults, other keys ignored).
+    P = N_samples + N_importance; `sampler`: the sampler's arguments (neus.py:733-738) under hip.neus_sample's / hip.neus_render's names."""
+    ra = SimpleNamespace(**{k: render_kwargs.get(k, v) for k, v in _ARG_DEFAULTS.items()})
+    ra.P = ra.N_samples + ra.N_importance
+    ra.sampler = dict(obj_bounding_radius=ra.obj_bounding_radius, n_samples=ra.N_samples, n_importance=ra.N_importance,
+                      n_upsample_iters=ra.N_upsample_iters, upsample_algo=ra.upsample_algo, n_nograd_samples=ra.N_nograd_samples,
+                      fixed_s_recp=ra.fixed_s_recp)
+    return ra
 
 
 class SingleRenderer(nn.Module):

@@ -21,6 +21,10 @@ perturb=True as well (a deviation: the gradient is then taken at the samples the
 
 Other differences from the reference, all deliberate: several reference patches share one launch group
 (per-patch eikonal means kept); NeuS keeps `radiance_net` frozen exactly like neus.py:455-456.
+
+Stated once each: the render kwargs are read by the framework's own `render_args` (the defaults of ITS volume_render signature, so both passes
+sample with the same settings); VolSDF's staged pass 1 is `_volsdf_depths` + `_volsdf_point_state` under the loop of `_staged_pass1` (render_keep,
+render_two_draws; `_samples` shares the depths); `_pass1` picks the pass 1 of a step.
 """
 import warnings
 
@@ -28,7 +32,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import autodiff, hip
+from . import autodiff, hip, neus, volsdf
 from . import dist as nd
 from .nets import NeuS, VolSDF
 
@@ -126,13 +130,21 @@ class Trainer(nn.Module):
                           "sampler - call calibrate_sampler() again before rendering with the trained weights")
             m.set_sampler_precision("fp16x2", guard=m.sampler_guard, late_round=m.sampler_late_round)
 
+    def _render_args(self, render_kwargs):
+        """The render kwargs as the framework's own volume_render reads them (volsdf / neus.render_args: its defaults, its refusals)."""
+        return (neus if self.is_neus else volsdf).render_args(render_kwargs)
+
+    def _ab(self):
+        alpha, beta = self.model.forward_ab()
+        return float(alpha.detach()), float(beta.detach())
+
     def resamples(self, render_kwargs) -> bool:
         """Does pass 2 of a fine-tune step with these render kwargs run the sampler again (module docstring)?"""
         if self.reuse_pass1_samples:
             return False
         if self.resample_pass2 is not None:
             return bool(self.resample_pass2)
-        return bool(render_kwargs.get("perturb", False))
+        return bool(self._render_args(render_kwargs).perturb)
 
     def shares_algorithm1(self, render_kwargs) -> bool:
         """Pass 2 re-samples AND takes its samples from pass 1's run of Algorithm 1 (render_two_draws): native VolSDF steps."""
@@ -162,9 +174,10 @@ class Trainer(nn.Module):
         self._training_sampler()
         kw = dict(render_kwargs)
         kw.pop("rayschunk", None)
-        if kw.get("perturb", False) and self.uniform_source is not None:
+        ra = self._render_args(kw)
+        if ra.perturb and self.uniform_source is not None:
             n = rays_o.reshape(-1, 3).shape[0]
-            kw["uniforms"] = self._uniform(1, 0, n, kw.get("N_importance", 64), rays_o.device)
+            kw["uniforms"] = self._uniform(1, 0, n, ra.N_importance, rays_o.device)
         rgb, depth, extras = render_fn(rays_o, rays_d, detailed_output=want_depths, require_nablas=True, calc_normal=True, **kw)
         if want_depths:
             d = extras["d_all" if self.is_neus else "d_vals"]
@@ -175,39 +188,71 @@ class Trainer(nn.Module):
     def _samples(self, o, dn, d_raw, rk, pass_no: int = 2, first_ray: int = 0):
         """Sample depths of a patch (no grad): the HIP sampler.  perturb=True draws the uniform numbers of the inverse-CDF
         samples from torch's generator (a fresh draw per call, as the reference's two passes draw separately)."""
-        m = self.model
-        surf_blob, rad_blob = m.packed()
-        perturb = bool(rk.get("perturb", False))
+        ra = self._render_args(rk)
+        u = self._uniform(pass_no, first_ray, o.shape[0], ra.N_importance, o.device) if ra.perturb else None
         if self.is_neus:
-            ni = rk.get("N_importance", 64)
             # the renderer's sampler on its own (its stage entry points: bit-identical depths, no frame rendered to get them)
-            return hip.neus_sample(surf_blob, o, d_raw, obj_bounding_radius=rk.get("obj_bounding_radius", 1.0), n_samples=rk.get("N_samples", 64),
-                                   n_importance=ni, n_upsample_iters=rk.get("N_upsample_iters", 4), precision=m.precision_id, **self._neus_algo(rk),
-                                   u_new=self._uniform(pass_no, first_ray, o.shape[0], ni, o.device) if perturb else None)
-        alpha, beta = m.forward_ab()
-        ns, ni = rk.get("N_samples", 128), rk.get("N_importance", 64)
-        near, far = rk.get("near", 0.0), rk.get("far", 6.0)
-        # model.set_sampler_precision(...): Algorithm 1 on its own blob / precision (it carries no gradient, volsdf.py:479; the per-sample
-        # state pass 2 differentiates is evaluated at the model's precision at whatever depths it returns)
-        sa = m.sampler_args()
-        d_fine, _, _ = hip.volsdf_fine_sample(sa["blob"], o, dn, near, far, rk.get("obj_bounding_radius", 3.0), float(alpha.detach()),
-                                              float(beta.detach()), rk.get("epsilon", 0.1), 4 * ns, 4 * ns, ni,
-                                              rk.get("max_upsample_steps", 5), rk.get("max_bisection_steps", 10),
-                                              precision=sa["precision"], escalate=sa["escalate"], guard=sa["guard"], late_round=sa["late_round"],
-                                              u_final=self._uniform(pass_no, first_ray, o.shape[0], ni, o.device) if perturb else None)
-        t = hip.lin_table(ns, o.device)
-        d_coarse = (near * (1.0 - t) + far * t)[None, :].expand(o.shape[0], ns)
-        return torch.sort(torch.cat([d_coarse, d_fine], dim=-1), dim=-1)[0]
-
-    @staticmethod
-    def _neus_algo(rk) -> dict:
-        """The up-sampling algorithm of the NeuS render kwargs (neus.py:733-736) in hip.neus_render's terms."""
-        return dict(upsample_algo=rk.get("upsample_algo", "official_solution"), n_nograd_samples=rk.get("N_nograd_samples", 2048),
-                    fixed_s_recp=rk.get("fixed_s_recp", 1 / 64.))
+            return hip.neus_sample(self.model.packed()[0], o, d_raw, precision=self.model.precision_id, u_new=u, **ra.sampler)
+        return self._volsdf_depths(o, dn, ra, None if u is None else [u], self._ab())[0]
 
     def _launch_rays(self, P: int) -> int:
         k = max(1, min(self.patches_per_launch, (1 << 21) // max(self.pass2_rays * P, 1)))
         return self.pass2_rays * k
+
+    # ---- VolSDF's pass 1 stage by stage: THE statement of what pass 2 (nerfart_volsdf_render_bwd) re-derives or is handed ---------
+    def _volsdf_depths(self, o, dn, ra, draws, ab):
+        """ONE run of Algorithm 1 for a batch of rays (dn: normalised) -> a list of sorted depths [n, P], one per draw: coarse + that draw's fine
+        samples.  draws: None (deterministic: one entry) or a list of [n, N_importance] uniform tensors, handed to the sampler side by side (bit-identical
+        to a run per draw: tests).  Algorithm 1 runs on the model's sampler blob / precision (set_sampler_precision; it carries no gradient, volsdf.py:479)."""
+        sa = self.model.sampler_args()
+        ns, ni, k = ra.N_samples, ra.N_importance, len(draws) if draws else 1
+        d_fine, _, _ = hip.volsdf_fine_sample(sa["blob"], o, dn, ra.near, ra.far, ra.obj_bounding_radius, ab[0], ab[1], ra.epsilon, 4 * ns, 4 * ns,
+                                              k * ni, ra.max_upsample_steps, ra.max_bisection_steps, precision=sa["precision"],
+                                              escalate=sa["escalate"], guard=sa["guard"], late_round=sa["late_round"],
+                                              u_final=torch.cat(draws, dim=1).contiguous() if draws else None)
+        t = hip.lin_table(ns, o.device)
+        d_coarse = (ra.near * (1.0 - t) + ra.far * t)[None, :].expand(o.shape[0], ns)
+        return [torch.sort(torch.cat([d_coarse, d_fine[:, c * ni:(c + 1) * ni]], dim=-1), dim=-1)[0] for c in range(k)]
+
+    def _volsdf_point_state(self, o, dn, depths, ra, ab):
+        """One launch group at its depths [R, P] in the fused renderer's order (points, sdf + nabla, radiance, composite) -> (rgb [R, 3], sdf, nablas, h7):
+        the state nerfart_volsdf_render_bwd computes for itself with have_state = 0 (dn from hip.normalize_dirs, the kernel it normalises with)."""
+        m = self.model
+        surf_blob, rad_blob = m.packed()
+        pts, v = hip.ray_points(o, dn, depths)
+        sdf, nab, h7 = hip.sdf_nabla_fwd(surf_blob, pts, m.obj_bounding_radius, precision=m.precision_id)
+        rgb_pt = hip.radiance_fwd(rad_blob, m.view_tiles, pts, v, nab, h7, precision=m.precision_id)
+        rgb, _, _ = hip.volsdf_composite(depths, sdf.reshape(-1, ra.P), rgb_pt.reshape(-1, ra.P, 3), ab[0], ab[1], ra.white_bkgd)
+        return rgb, sdf, nab, h7
+
+    def _staged_pass1(self, rays_o, rays_d, rk, two_draws: bool):
+        """VolSDF's pass 1 on the stages above -> rgb [N, 3]: one set of sampler launches per pass1_groups of pass 2's launch groups, the per-point state
+        group by group.  two_draws False: every group's (depths, sdf, nablas, h7) is left in self._kept; True: the sampler gets pass 1's and pass 2's
+        draw, the image is evaluated at the first, the state is dropped and the depths of the second are left in self._depths2 [N, P]."""
+        ra = self._render_args(rk)                            # refuses what volume_render refuses
+        o, d_raw = (r.reshape(-1, 3).float().contiguous() for r in (rays_o, rays_d))
+        ab = self._ab()
+        step = self._launch_rays(ra.P)
+        big = step * self.pass1_groups
+        draw_passes = (1, 2) if two_draws else (1,) if ra.perturb else ()     # whose uniform numbers the sampler is handed
+        kept, rgbs, deps2 = [], [], []
+        for i in range(0, o.shape[0], big):
+            oi, dn = o[i:i + big], hip.normalize_dirs(d_raw[i:i + big])
+            draws = [self._uniform(p, i, oi.shape[0], ra.N_importance, o.device) for p in draw_passes]
+            deps = self._volsdf_depths(oi, dn, ra, draws, ab)
+            deps2 += deps[1:]
+            for j in range(0, oi.shape[0], step):                 # pass 2's launch groups: their OWN tensors, freed group by group
+                dj = deps[0][j:j + step].contiguous()
+                rgb, sdf, nab, h7 = self._volsdf_point_state(oi[j:j + step], dn[j:j + step], dj, ra, ab)
+                rgbs.append(rgb)
+                if not two_draws:
+                    kept.append((dj, sdf, nab, h7))
+                del sdf, nab, h7
+        if two_draws:
+            self._depths2 = torch.cat(deps2, 0) if deps2 else torch.zeros(0, ra.P, device=o.device)
+        else:
+            self._kept = kept
+        return torch.cat(rgbs, 0) if rgbs else torch.zeros(0, 3, device=o.device)
 
     @torch.no_grad()
     def render_keep(self, rays_o, rays_d, **rk):
@@ -217,53 +262,24 @@ class Trainer(nn.Module):
         deterministic, so pass 2 would recompute exactly these.  Returns rgb [N, 3]; the state waits in self._kept."""
         self._training_sampler()
         m = self.model
-        if not self.is_neus:
-            from .volsdf import check_render_kwargs
-            check_render_kwargs(**rk)                 # the staged pass 1 refuses what volume_render refuses
         if m.precision != "bf16x3":
             raise RuntimeError("render_keep keeps split-bf16 pass-1 state for the native pass 2: set_precision('bf16x3') first")
-        o = rays_o.reshape(-1, 3).float().contiguous()
-        d_raw = rays_d.reshape(-1, 3).float().contiguous()
-        surf_blob, rad_blob = m.packed()
-        if self.is_neus:
-            # NeuS: the fused renderer's detailed outputs already hold what pass 2 needs at the P samples (depths, sdf,
-            # nablas); the mid-point quantities are re-evaluated in pass 2
-            ni = rk.get("N_importance", 64)
-            P = rk.get("N_samples", 64) + ni
-            step = self._launch_rays(P)
-            s_val = float(m.forward_s().detach())
-            kept, rgbs = [], []
-            for i in range(0, o.shape[0], step):
-                oi, di = o[i:i + step], d_raw[i:i + step]
-                out = hip.neus_render(surf_blob, rad_blob, m.view_tiles, oi, di, obj_bounding_radius=rk.get("obj_bounding_radius", 1.0),
-                                      s=s_val, n_samples=rk.get("N_samples", 64), n_importance=ni,
-                                      n_upsample_iters=rk.get("N_upsample_iters", 4), white_bkgd=rk.get("white_bkgd", False),
-                                      calc_normal=False, detailed=True, precision=m.precision_id, **self._neus_algo(rk),
-                                      u_new=self._uniform(1, i, oi.shape[0], ni, o.device) if rk.get("perturb", False) else None)
-                kept.append((out["d_all"], out["implicit_surface"].reshape(-1), out["implicit_nablas"].reshape(-1, 3), None))
-                rgbs.append(out["rgb"])
-            self._kept = kept
-            return torch.cat(rgbs, 0) if rgbs else torch.zeros(0, 3, device=o.device)
-        alpha, beta = m.forward_ab()
-        ab = (float(alpha.detach()), float(beta.detach()))
-        white = rk.get("white_bkgd", False)
-        P = rk.get("N_samples", 128) + rk.get("N_importance", 64)
-        step = self._launch_rays(P)
-        big = step * self.pass1_groups
+        if not self.is_neus:
+            return self._staged_pass1(rays_o, rays_d, rk, two_draws=False)
+        # NeuS: the fused renderer's detailed outputs already hold what pass 2 needs at the P samples (depths, sdf,
+        # nablas); the mid-point quantities are re-evaluated in pass 2
+        ra = self._render_args(rk)
+        o, d_raw = (r.reshape(-1, 3).float().contiguous() for r in (rays_o, rays_d))
+        step = self._launch_rays(ra.P)
+        s_val = float(m.forward_s().detach())
         kept, rgbs = [], []
-        for i in range(0, o.shape[0], big):
-            oi, di = o[i:i + big], d_raw[i:i + big]
-            dn = hip.normalize_dirs(di)                                   # the kernel nerfart_volsdf_render_bwd normalises with: same points
-            depths = self._samples(oi, dn, di, rk, 1, i).contiguous()     # one set of sampler launches for pass1_groups launch groups
-            for j in range(0, oi.shape[0], step):                         # pass 2's launch groups: their OWN tensors, freed group by group
-                dj = depths[j:j + step].contiguous()
-                Rj = dj.shape[0]
-                pts, v = hip.ray_points(oi[j:j + step], dn[j:j + step], dj)
-                sdf, nab, h7 = hip.sdf_nabla_fwd(surf_blob, pts, m.obj_bounding_radius, precision=m.precision_id)
-                rgb_pt = hip.radiance_fwd(rad_blob, m.view_tiles, pts, v, nab, h7, precision=m.precision_id)
-                rgb, _, _ = hip.volsdf_composite(dj, sdf.reshape(Rj, P), rgb_pt.reshape(Rj, P, 3), ab[0], ab[1], white)
-                kept.append((dj, sdf, nab, h7))
-                rgbs.append(rgb)
+        for i in range(0, o.shape[0], step):
+            oi, di = o[i:i + step], d_raw[i:i + step]
+            out = hip.neus_render(*m.packed(), m.view_tiles, oi, di, s=s_val, white_bkgd=ra.white_bkgd, calc_normal=False, detailed=True,
+                                  precision=m.precision_id, **ra.sampler,
+                                  u_new=self._uniform(1, i, oi.shape[0], ra.N_importance, o.device) if ra.perturb else None)
+            kept.append((out["d_all"], out["implicit_surface"].reshape(-1), out["implicit_nablas"].reshape(-1, 3), None))
+            rgbs.append(out["rgb"])
         self._kept = kept
         return torch.cat(rgbs, 0) if rgbs else torch.zeros(0, 3, device=o.device)
 
@@ -275,49 +291,11 @@ class Trainer(nn.Module):
         depths of the second set wait in self._depths2 [N, P] for backward_patches(depths_all=...), whose nerfart_volsdf_render_bwd
         (have_state = 0) evaluates the per-point state there.  Returns rgb [N, 3]."""
         self._training_sampler()
-        m = self.model
         if self.is_neus:
             raise RuntimeError("render_two_draws: VolSDF only (NeuS draws in every up-sampling round)")
-        from .volsdf import check_render_kwargs
-        check_render_kwargs(**rk)                     # the staged pass 1 refuses what volume_render refuses
-        if m.precision != "bf16x3":
+        if self.model.precision != "bf16x3":
             raise RuntimeError("render_two_draws feeds the native pass 2: set_precision('mixed') or ('bf16x3') first")
-        o = rays_o.reshape(-1, 3).float().contiguous()
-        d_raw = rays_d.reshape(-1, 3).float().contiguous()
-        surf_blob, rad_blob = m.packed()
-        sa = m.sampler_args()
-        alpha, beta = m.forward_ab()
-        ab = (float(alpha.detach()), float(beta.detach()))
-        white = rk.get("white_bkgd", False)
-        ns, ni = rk.get("N_samples", 128), rk.get("N_importance", 64)
-        near, far = rk.get("near", 0.0), rk.get("far", 6.0)
-        P = ns + ni
-        step = self._launch_rays(P)
-        big = step * self.pass1_groups
-        t = hip.lin_table(ns, o.device)
-        rgbs, deps2 = [], []
-        for i in range(0, o.shape[0], big):
-            oi, di = o[i:i + big], d_raw[i:i + big]
-            n = oi.shape[0]
-            dn = hip.normalize_dirs(di)
-            u = torch.cat([self._uniform(1, i, n, ni, o.device), self._uniform(2, i, n, ni, o.device)], dim=1).contiguous()
-            d_fine, _, _ = hip.volsdf_fine_sample(sa["blob"], oi, dn, near, far, rk.get("obj_bounding_radius", 3.0), ab[0], ab[1], rk.get("epsilon", 0.1),
-                                                  4 * ns, 4 * ns, 2 * ni, rk.get("max_upsample_steps", 5), rk.get("max_bisection_steps", 10),
-                                                  precision=sa["precision"], escalate=sa["escalate"], guard=sa["guard"], late_round=sa["late_round"], u_final=u)
-            d_coarse = (near * (1.0 - t) + far * t)[None, :].expand(n, ns)
-            dep1 = torch.sort(torch.cat([d_coarse, d_fine[:, :ni]], dim=-1), dim=-1)[0]
-            deps2.append(torch.sort(torch.cat([d_coarse, d_fine[:, ni:]], dim=-1), dim=-1)[0])
-            for j in range(0, n, step):
-                dj = dep1[j:j + step].contiguous()
-                Rj = dj.shape[0]
-                pts, v = hip.ray_points(oi[j:j + step], dn[j:j + step], dj)
-                sdf, nab, h7 = hip.sdf_nabla_fwd(surf_blob, pts, m.obj_bounding_radius, precision=m.precision_id)
-                rgb_pt = hip.radiance_fwd(rad_blob, m.view_tiles, pts, v, nab, h7, precision=m.precision_id)
-                rgb, _, _ = hip.volsdf_composite(dj, sdf.reshape(Rj, P), rgb_pt.reshape(Rj, P, 3), ab[0], ab[1], white)
-                rgbs.append(rgb)
-                del sdf, nab, h7, rgb_pt
-        self._depths2 = torch.cat(deps2, 0) if deps2 else torch.zeros(0, P, device=o.device)
-        return torch.cat(rgbs, 0) if rgbs else torch.zeros(0, 3, device=o.device)
+        return self._staged_pass1(rays_o, rays_d, rk, two_draws=True)
 
     def backward_patches(self, rays_o, rays_d, gradient, depths_all=None, kept=None, **render_kwargs):
         """Pass 2: accumulates parameter gradients for d loss / d rgb = `gradient` [N, 3] (+ the eikonal term).
@@ -329,18 +307,12 @@ class Trainer(nn.Module):
         d_all_ = rays_d.reshape(-1, 3).float().contiguous()
         g_all = gradient.reshape(-1, 3)
         N = o_all.shape[0]
-        white = render_kwargs.get("white_bkgd", False)
+        ra = self._render_args(render_kwargs)
         eik_sum, n = 0.0, 0
         if self.native:
             accum = autodiff.GradAccumulator()                    # raw GEMM results summed over patches, flushed once
-            ab = s_val = None
-            if self.is_neus:
-                s_val = float(self.model.forward_s().detach())
-                P = render_kwargs.get("N_samples", 64) + render_kwargs.get("N_importance", 64)
-            else:
-                alpha, beta = self.model.forward_ab()
-                ab = (float(alpha.detach()), float(beta.detach()))
-                P = render_kwargs.get("N_samples", 128) + render_kwargs.get("N_importance", 64)
+            s_val = float(self.model.forward_s().detach()) if self.is_neus else None
+            ab = None if self.is_neus else self._ab()
             if kept is not None:
                 bounds, i = [], 0
                 for grp in kept:
@@ -349,7 +321,7 @@ class Trainer(nn.Module):
                 if i != N:
                     raise ValueError("backward_patches: the kept pass-1 state does not cover these rays")
             else:
-                step = self._launch_rays(P)
+                step = self._launch_rays(ra.P)
                 bounds = [(i, min(i + step, N)) for i in range(0, N, step)]
             fresh, fresh_lo = None, 0                              # re-sampled depths of the current batch of launch groups
             for gi, (i0, i1) in enumerate(bounds):
@@ -370,10 +342,10 @@ class Trainer(nn.Module):
                         fresh_lo = i0
                     depths = fresh[i0 - fresh_lo:i1 - fresh_lo].contiguous()
                 if self.is_neus:
-                    eik = autodiff.neus_backward_samples_native(self.model, o, d_raw, depths, g, self.w_eikonal, self.use_eikonal, white,
+                    eik = autodiff.neus_backward_samples_native(self.model, o, d_raw, depths, g, self.w_eikonal, self.use_eikonal, ra.white_bkgd,
                                                                 s_val=s_val, accum=accum, eik_group_rays=self.pass2_rays, state=state)
                 else:
-                    eik = autodiff.volsdf_backward_samples_native(self.model, o, d_raw, depths, g, self.w_eikonal, self.use_eikonal, white,
+                    eik = autodiff.volsdf_backward_samples_native(self.model, o, d_raw, depths, g, self.w_eikonal, self.use_eikonal, ra.white_bkgd,
                                                                   ab=ab, accum=accum, state=state, eik_group_rays=self.pass2_rays)
                 eik_sum = eik_sum + eik
                 n += -(-(i1 - i0) // self.pass2_rays)
@@ -386,7 +358,7 @@ class Trainer(nn.Module):
             with torch.no_grad():
                 depths = self._samples(o, dn, d_raw, render_kwargs, 2, i) if depths_all is None else depths_all[i:i + self.pass2_rays].contiguous()
             fn = autodiff.neus_render_samples if self.is_neus else autodiff.volsdf_render_samples
-            out = fn(self.model, o, dn, depths, white_bkgd=white)
+            out = fn(self.model, o, dn, depths, white_bkgd=ra.white_bkgd)
             if self.use_eikonal:
                 # the reference calls rgb.backward(g, retain_graph=True) and then eikonal.backward(): the same sum of
                 # gradients from ONE traversal of the (double-backward) graph of the SDF net
@@ -422,6 +394,7 @@ class Trainer(nn.Module):
         d = rays_d.reshape(-1, 3).float().contiguous()
         N = o.shape[0]
         kw = {k: v for k, v in render_kwargs.items() if k != "rayschunk"}
+        white = self._render_args(kw).white_bkgd
         with torch.no_grad():
             rgb, _, ex = render_fn(o[None], d[None], detailed_output=True, require_nablas=True, calc_normal=True, **kw)
             rgb = rgb.reshape(N, 3)
@@ -453,21 +426,19 @@ class Trainer(nn.Module):
             optimizer.zero_grad()
         dn = F.normalize(d, dim=-1)
         if self.native:
-            alpha, beta = m.forward_ab()
-            ab = (float(alpha.detach()), float(beta.detach()))
+            ab = self._ab()
             accum = autodiff.GradAccumulator()
             for i in range(0, N, self.pass2_rays):
                 sl = slice(i, i + self.pass2_rays)
                 autodiff.volsdf_backward_samples_native(m, o[sl], d[sl], depths[sl].contiguous(), g_rgb[sl], use_eikonal=False,
-                                                        white_bkgd=kw.get("white_bkgd", False), ab=ab, nbar_extra=nbar_extra[sl],
-                                                        accum=accum)
+                                                        white_bkgd=white, ab=ab, nbar_extra=nbar_extra[sl], accum=accum)
             with torch.no_grad():
                 autodiff.surface_param_backward(m, eikonal_points.reshape(-1, 3).float().contiguous(), g_eik.contiguous(), accum=accum)
             accum.flush(m)
         else:
             for i in range(0, N, self.pass2_rays):
                 sl = slice(i, i + self.pass2_rays)
-                out = autodiff.volsdf_render_samples(m, o[sl], dn[sl], depths[sl].contiguous(), white_bkgd=kw.get("white_bkgd", False))
+                out = autodiff.volsdf_render_samples(m, o[sl], dn[sl], depths[sl].contiguous(), white_bkgd=white)
                 torch.autograd.backward([out["rgb"], out["implicit_nablas"]], [g_rgb[sl], nbar_extra[sl]])
             _, nab_e, _ = autodiff.surface_forward_with_nablas(m.implicit_surface, eikonal_points.reshape(-1, 3).float())
             nab_e.backward(g_eik)
@@ -480,7 +451,7 @@ class Trainer(nn.Module):
         d = rays_d.reshape(-1, 3).float().contiguous()
         N = o.shape[0]
         kw = {k: v for k, v in render_kwargs.items() if k != "rayschunk"}
-        white = kw.get("white_bkgd", False)
+        white = self._render_args(kw).white_bkgd
         with torch.no_grad():
             rgb, _, ex = render_fn(o[None], d[None], detailed_output=True, calc_normal=False, **kw)
             rgb = rgb.reshape(N, 3)
@@ -581,6 +552,18 @@ class Trainer(nn.Module):
             extras["scalars"] = {"beta": beta.data, "alpha": alpha.data}
         return OrderedDict([("losses", losses), ("extras", extras)])
 
+    def _pass1(self, render_fn, rays_o, rays_d, keep: bool, share: bool, resample: bool, **rk):
+        """Pass 1 of a fine-tune step -> (rgb [N, 3], the depths [N, P] pass 2 is to use or None).  keep: state left in self._kept; share: pass 2's depths
+        from pass 1's run of Algorithm 1; otherwise the fused renderer - resample: nothing kept, pass 2 samples again; else its depths."""
+        if keep:
+            return self.render_keep(rays_o, rays_d, **rk), None
+        if share:
+            return self.render_two_draws(rays_o, rays_d, **rk), self._depths2
+        if resample:
+            return self.render_image(render_fn, rays_o, rays_d, **rk).reshape(-1, 3), None
+        rgb, depths = self.render_image(render_fn, rays_o, rays_d, want_depths=True, **rk)
+        return rgb.reshape(-1, 3), depths
+
     # ---- one fine-tune step ---------------------------------------------------------------------------
     def finetune_step(self, render_fn, rays_o, rays_d, target_rgb, H: int, style_loss, optimizer=None, tile: int = None,
                       **render_kwargs):
@@ -604,31 +587,16 @@ class Trainer(nn.Module):
             kw = {k: v for k, v in render_kwargs.items() if k != "rayschunk"}
             n_frame = rays_o.reshape(-1, 3).shape[0]
             self._global_rays = (nd.shard_plan(n_frame, tile, rays_o.device).idx, n_frame)
-            if keep:
-                def fn(ro, rd, **kw_):
-                    r = self.render_keep(ro, rd, **kw_)
-                    return r, None, {"rgb": r[None]}
-            elif share:
-                def fn(ro, rd, **kw_):
-                    r = self.render_two_draws(ro, rd, **kw_)
-                    return r, None, {"rgb": r[None]}
-            else:
-                def fn(ro, rd, **kw_):
-                    kw_ = {k: v for k, v in kw_.items() if k not in ("detailed_output", "require_nablas", "calc_normal")}
-                    r = self.render_image(render_fn, ro, rd, **kw_)
-                    return r, None, {"rgb": r.reshape(1, -1, 3)}
+            def fn(ro, rd, **kw_):
+                kw_ = {k: v for k, v in kw_.items() if k not in ("detailed_output", "require_nablas", "calc_normal")}
+                # a rank that neither keeps nor shares renders WITHOUT keeping depths (resample=True): its pass 2 samples again
+                r = self._pass1(render_fn, ro, rd, keep, share, True, **kw_)[0]
+                return r, None, {"rgb": r[None]}
             rgb = nd.render_sharded(fn, rays_o.reshape(1, -1, 3), rays_d.reshape(1, -1, 3), keys=("rgb",), tile=tile,
                                     detailed_output=False, require_nablas=True, calc_normal=True, **kw)["rgb"]
-            depths_all = None
-        elif keep:
-            rgb, depths_all = self.render_keep(rays_o, rays_d, **render_kwargs), None
-        elif share:
-            rgb = self.render_two_draws(rays_o, rays_d, **render_kwargs)
             depths_all = self._depths2
-        elif resample:
-            rgb, depths_all = self.render_image(render_fn, rays_o, rays_d, **render_kwargs), None
         else:
-            rgb, depths_all = self.render_image(render_fn, rays_o, rays_d, want_depths=True, **render_kwargs)
+            rgb, depths_all = self._pass1(render_fn, rays_o, rays_d, keep, share, resample, **render_kwargs)
         rgb = rgb.detach().reshape(1, -1, 3).requires_grad_(True)
         W = rgb.shape[1] // H
         to_img = lambda t: t.reshape(t.shape[0], H, W, 3).permute(0, 3, 1, 2)          # "B (H W) C -> B C H W"
@@ -640,7 +608,7 @@ class Trainer(nn.Module):
         if sharded:
             idx = nd.shard_plan(rgb.shape[1], tile, rgb.device).idx          # cached per (frame size, tile, world)
             eik = self.backward_patches(rays_o.reshape(-1, 3)[idx], rays_d.reshape(-1, 3)[idx], gradient[0][idx], kept=self._kept,
-                                        depths_all=self._depths2, **render_kwargs)
+                                        depths_all=depths_all, **render_kwargs)
             # ranks that own fewer parameters' gradients than others (none here: every rank touches every tensor)
             for p in self.model.parameters():
                 if p.requires_grad and p.grad is None:

@@ -15,7 +15,9 @@ materialises and drops in ``fine_sample`` never exists; weight_norm is folded on
 from __future__ import annotations
 
 import copy
+import inspect
 from collections import OrderedDict
+from types import SimpleNamespace
 
 import torch
 import torch.nn as nn
@@ -106,6 +108,19 @@ def volume_render(rays_o, rays_d, model: VolSDF, near=0.0, far=6.0, obj_bounding
         ret["alpha"] = 1.0 - ret["p_i"]
         ret["beta_map"] = ret["beta_map"].unsqueeze(-1)          # reference shape [(B), N_rays, 1] (volsdf.py:590)
     return ret["rgb"], ret["depth_volume"], ret
+
+
+_ARG_DEFAULTS = {k: inspect.signature(volume_render).parameters[k].default for k in (
+    "near", "far", "obj_bounding_radius", "epsilon", "N_samples", "N_importance", "max_upsample_steps", "max_bisection_steps", "white_bkgd", "perturb")}
+
+
+def render_args(render_kwargs) -> SimpleNamespace:
+    """The sampling and compositing arguments of a set of render kwargs as volume_render itself reads them (how the Trainer's passes read them): its signature's
+    defaults (above: there is no second table), the caller's values over them, other keys ignored, what it refuses refused.  P = N_samples + N_importance."""
+    check_render_kwargs(**render_kwargs)
+    ra = SimpleNamespace(**{k: render_kwargs.get(k, v) for k, v in _ARG_DEFAULTS.items()})
+    ra.P = ra.N_samples + ra.N_importance
+    return ra
 
 
 class SingleRenderer(nn.Module):
