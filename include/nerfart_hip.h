@@ -49,7 +49,8 @@
 extern "C" {
 #endif
 
-/* 5 (round 6, second session).  History: 4 -> 5, additions only: nerfart_volsdf_fine_sample_guarded2 / nerfart_volsdf_render_staged2_fwd (the guarded sampler's
+/* 5 (round 6, second session; since then additions only, marked "addition to ABI 5" where they are declared: the mesh entry points,
+ * nerfart_volsdf_composite_geo_bwd, nerfart_volsdf_render_bwd2).  History: 4 -> 5, additions only: nerfart_volsdf_fine_sample_guarded2 / nerfart_volsdf_render_staged2_fwd (the guarded sampler's
  * `late_round`), C-ABI precision 5 on the SDF-only entry points.
  * 3 -> 4, additions only: the guarded sampler (nerfart_volsdf_fine_sample_guarded) and the per-stage-precision renderer
  * (nerfart_volsdf_render_staged_fwd), nerfart_pack_layer_dims, nerfart_geometry_feature.
@@ -231,6 +232,27 @@ int nerfart_volsdf_composite_bwd(int n_rays, int P, const float* d_all, const fl
  * 2 <= P <= 513, as nerfart_volsdf_composite_bwd; any other P is refused with 2 before any HIP call. */
 int nerfart_neus_composite_bwd(int n_rays, int P, const float* sdf, const float* rad_mid, float s, int white_bkgd, const float* g_rgb,
                                const float* g_acc, float* g_sdf, float* g_rad_mid, float* g_s, void* stream);
+
+/* Backward of nerfart_volsdf_composite w.r.t. its DEPTH and NORMALS outputs (csrc/volsdf_geo_backward.hip; an addition to ABI 5, no counterpart in
+ * the reference, whose losses read rgb only): the geometry terms of a fine-tune objective - depth preservation, normal consistency, smoothness.
+ * VolSDF only.  With tau_k = (1 - p_k + 1e-10) T_k over the first P - 1 samples, acc = sum tau_k, inv = acc + 1e-10, depth = sum tau_k d_k / inv,
+ * normals = sum tau_k n_k, n_k = nabla_k / max(|nabla_k|, 1e-12) (the forward's values, recomputed here with its expressions):
+ *     g_tau_k   = g_normals . n_k + (g_depth / inv) (d_k - depth)         then g_sdf, d / d alpha, d / d beta as nerfart_volsdf_composite_bwd from ITS g_tau
+ *     g_nabla_k = tau_k (g_normals - n_k (n_k . g_normals)) / |nabla_k|    where |nabla_k| >= 1e-12,   tau_k g_normals / 1e-12 below that (F.normalize's
+ *                 clamp_min as autograd differentiates it);  0 for the last sample, which carries no weight.   The sample depths carry no gradient.
+ *   g_depth [R], g_normals [R,3]: each may be NULL (= zero), not both.  nabla [R,P,3] and g_nabla [R,P,3] are required iff g_normals is given;
+ *   without g_normals neither is touched.
+ *   g_n_in [R,P,3] or NULL: added into g_nabla when g_nabla is written (g_nabla = g_n_in is allowed: each element is read, then written, by one lane) - the
+ *   result goes straight into the g_n_extra slot of nerfart_volsdf_pass2_cotangents.  Not read when g_nabla is not written.
+ *   accumulate != 0: g_sdf [R,P] += (the last sample's entry untouched); else g_sdf = , the last sample's entry written as +0.
+ *   g_alpha_beta[2] += (d / d alpha, d / d beta), accumulated with atomics as in nerfart_volsdf_composite_bwd; may be NULL.
+ *   EMPTY RAYS: (d_k - depth) / inv grows without bound as acc -> 0 (inv -> 1e-10): the depth cotangent of a ray that hits nothing is amplified by up
+ *   to 1e10, as autograd through the reference's tau / (acc + 1e-10) amplifies it.  Nothing is clamped: weight a depth loss with the opacity.
+ * n_rays <= 0 is a no-op.  P < 2, P > 513 (a lane holds at most 8 intervals in registers) or a missing required pointer is refused with 2 and
+ * nerfart_last_error set, before any HIP call. */
+int nerfart_volsdf_composite_geo_bwd(int n_rays, int P, const float* d_all, const float* sdf, const float* nabla, float alpha, float beta,
+                                     const float* g_depth, const float* g_normals, const float* g_n_in, int accumulate, float* g_sdf,
+                                     float* g_nabla, float* g_alpha_beta, void* stream);
 
 /* ---- B1: VolSDF volume_render (volsdf.py:389-615) for one chunk of rays (rays_d un-normalised). */
 long long nerfart_volsdf_render_workspace_bytes(int n_rays, int n_samples, int n_importance, int max_upsample_steps,
@@ -585,6 +607,18 @@ int nerfart_volsdf_render_bwd(const float* surf_blob, const float* rad_blob, int
                               const float* sdf_state, const float* nabla_state, const float* h7_state, float R_bg, float alpha, float beta,
                               int white_bkgd, float w_eikonal, int eik_group_rays, int train_radiance, float* raw, void* workspace,
                               long long workspace_bytes, void* stream);
+/* (addition to ABI 5) nerfart_volsdf_render_bwd plus the cotangents of the depth and normals maps: g_depth [n_rays] / g_normals [n_rays, 3], each may be NULL.
+ * After nerfart_volsdf_composite_bwd, nerfart_volsdf_composite_geo_bwd (above: formulas, the empty-ray caveat) adds their share to g_sdf and to the
+ * (alpha, beta) scalars of raw, and its nabla cotangent (which already includes g_n_extra) takes g_n_extra's place in nerfart_volsdf_pass2_cotangents;
+ * everything after that is nerfart_volsdf_render_bwd's sequence.  Workspace: nerfart_volsdf_render_bwd2_workspace_bytes(n_rays, P, have_state,
+ * have_normals = g_normals != NULL) - nerfart_volsdf_render_bwd's plus, with normals, one [n_rays P, 3] buffer.  Both NULL: exactly
+ * nerfart_volsdf_render_bwd (same launches, same order, same workspace size).  VolSDF only: the NeuS entry point has no such cotangents. */
+long long nerfart_volsdf_render_bwd2_workspace_bytes(int n_rays, int P, int have_state, int have_normals);
+int nerfart_volsdf_render_bwd2(const float* surf_blob, const float* rad_blob, int view_tiles, int multires, const float* rays_o, const float* rays_d,
+                               int n_rays, int P, const float* d_all, const float* g_rgb, const float* g_acc, const float* g_n_extra,
+                               const float* g_depth, const float* g_normals, const float* sdf_state, const float* nabla_state, const float* h7_state,
+                               float R_bg, float alpha, float beta, int white_bkgd, float w_eikonal, int eik_group_rays, int train_radiance,
+                               float* raw, void* workspace, long long workspace_bytes, void* stream);
 long long nerfart_neus_render_bwd_workspace_bytes(int n_rays, int P, int have_state);
 int nerfart_neus_render_bwd(const float* surf_blob, const float* rad_blob, int view_tiles, int multires, const float* rays_o, const float* rays_d,
                             int n_rays, int P, const float* d_all, const float* g_rgb, const float* g_acc, const float* sdf_state,

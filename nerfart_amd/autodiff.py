@@ -180,7 +180,7 @@ def _native_backward(model, who: str, device, accum, call):
 
 
 def volsdf_backward_samples_native(model, rays_o, rays_d, d_all, g_rgb, w_eikonal=0.1, use_eikonal=True, white_bkgd=False, ab=None,
-                                   nbar_extra=None, accum=None, state=None, eik_group_rays=None, g_acc=None):
+                                   nbar_extra=None, accum=None, state=None, eik_group_rays=None, g_acc=None, g_depth=None, g_normals=None):
     """Pass 2 of the fine-tune step for one launch group of rays: ONE call of nerfart_volsdf_render_bwd, which accumulates into the
     step's raw buffer what rgb.backward(g_rgb) and (w_eikonal * MSE(|nabla|, 1)).backward() accumulate (volsdf.py:759-770).
     rays_d: un-normalised (the entry point normalises, as the forward does).  Returns the eikonal loss (a 0-d tensor: no host
@@ -189,7 +189,9 @@ def volsdf_backward_samples_native(model, rays_o, rays_d, d_all, g_rgb, w_eikona
     accum: a GradAccumulator shared by the launch groups of a step - the caller flushes it once; None: .grad is updated here.
     state: (sdf, nablas, h7) of these points kept from pass 1 (same weights: identical values) - skips their re-evaluation.
     eik_group_rays: the rays are several `eik_group_rays`-ray patches of the reference in one launch (the eikonal mean is
-    per patch); the returned loss is then the SUM over those patches."""
+    per patch); the returned loss is then the SUM over those patches.
+    g_acc [R] / g_depth [R] / g_normals [R, 3]: cotangents of the mask_volume, depth_volume and normals_volume maps (the last two go through
+    nerfart_volsdf_render_bwd2; a depth cotangent on an empty ray is amplified by 1 / (acc + 1e-10), as in the reference's autograd)."""
     from . import hip
     def call(raw):
         alpha, beta = ab if ab is not None else (float(x.detach()) for x in model.forward_ab())
@@ -198,7 +200,9 @@ def volsdf_backward_samples_native(model, rays_o, rays_d, d_all, g_rgb, w_eikona
                               white_bkgd=white_bkgd, w_eikonal=w_eikonal if use_eikonal else 0.0, eik_group_rays=eik_group_rays or 0,
                               train_radiance=any(p.requires_grad for p in model.radiance_net.parameters()), g_acc=None if g_acc is None else g_acc.contiguous(),
                               g_n_extra=None if nbar_extra is None else nbar_extra.reshape(-1, 3).contiguous(),
-                              state=None if state is None else tuple(t.contiguous() for t in state))
+                              state=None if state is None else tuple(t.contiguous() for t in state),
+                              g_depth=None if g_depth is None else g_depth.reshape(-1).float().contiguous(),
+                              g_normals=None if g_normals is None else g_normals.reshape(-1, 3).float().contiguous())
     return _native_backward(model, "volsdf_backward_samples_native", d_all.device, accum, call)
 
 

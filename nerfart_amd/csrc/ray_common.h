@@ -47,6 +47,17 @@ __device__ __forceinline__ float wave_excl_prod(float v) {
     const float e = __shfl_up(v, 1, 64);
     return lane == 0 ? 1.f : e;
 }
+// sum over the lanes AFTER this one (lane 63 gets 0)
+__device__ __forceinline__ float wave_excl_suffix_sum(float v) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float t = __shfl_down(v, o, 64);
+        if (lane + o < 64) v += t;
+    }
+    const float e = __shfl_down(v, 1, 64);
+    return lane == 63 ? 0.f : e;
+}
 
 // a11 sdf_to_sigma (reference models/frameworks/volsdf.py:34-53)
 __device__ __forceinline__ float sdf_to_sigma(float s, float alpha, float beta) {

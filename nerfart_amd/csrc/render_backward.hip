@@ -455,20 +455,36 @@ int nerfart_radiance_param_bwd(const float* rad_blob, int view_tiles, const floa
     return 0;
 }
 
-long long nerfart_volsdf_render_bwd_workspace_bytes(int n_rays, int P, int have_state) {
+// the workspace of nerfart_volsdf_render_bwd; with a normals cotangent (nerfart_volsdf_render_bwd2) one more [R P, 3] buffer BEHIND it: the nabla
+// cotangent of k_composite_volsdf_geo_bwd, which takes g_n_extra's place in nerfart_volsdf_pass2_cotangents
+static VolWs carve_volsdf2(Carver& c, long long R, int P, int have_state, int have_normals, float** g_nab) {
+    VolWs w = carve_volsdf(c, R, P, have_state);
+    float* g = have_normals ? c.take<float>((size_t)R * P * 3) : nullptr;
+    if (g_nab) *g_nab = g;
+    return w;
+}
+
+long long nerfart_volsdf_render_bwd2_workspace_bytes(int n_rays, int P, int have_state, int have_normals) {
     if (n_rays <= 0 || P < 2) return 0;
     Carver c(nullptr);
-    carve_volsdf(c, n_rays, P, have_state);
+    carve_volsdf2(c, n_rays, P, have_state, have_normals, nullptr);
     return (long long)c.off;
 }
 
-int nerfart_volsdf_render_bwd(const float* surf_blob, const float* rad_blob, int view_tiles, int multires, const float* rays_o, const float* rays_d,
-                              int n_rays, int P, const float* d_all, const float* g_rgb, const float* g_acc, const float* g_n_extra,
-                              const float* sdf_state, const float* nabla_state, const float* h7_state, float R_bg, float alpha, float beta,
-                              int white_bkgd, float w_eikonal, int eik_group_rays, int train_radiance, float* raw, void* workspace,
-                              long long workspace_bytes, void* stream) {
-    if (int rc_ = blob_term_check(surf_blob, 1, "nerfart_volsdf_render_bwd")) return rc_;
-    if (int rc_ = blob_term_check(rad_blob, 1, "nerfart_volsdf_render_bwd")) return rc_;
+long long nerfart_volsdf_render_bwd_workspace_bytes(int n_rays, int P, int have_state) {
+    return nerfart_volsdf_render_bwd2_workspace_bytes(n_rays, P, have_state, 0);
+}
+
+// g_depth == g_normals == NULL: nerfart_volsdf_render_bwd's launches, in its order, out of its workspace
+int nerfart_volsdf_render_bwd2(const float* surf_blob, const float* rad_blob, int view_tiles, int multires, const float* rays_o, const float* rays_d,
+                               int n_rays, int P, const float* d_all, const float* g_rgb, const float* g_acc, const float* g_n_extra,
+                               const float* g_depth, const float* g_normals, const float* sdf_state, const float* nabla_state, const float* h7_state,
+                               float R_bg, float alpha, float beta, int white_bkgd, float w_eikonal, int eik_group_rays, int train_radiance,
+                               float* raw, void* workspace, long long workspace_bytes, void* stream) {
+    const bool geo = g_depth || g_normals;
+    const char* who = geo ? "nerfart_volsdf_render_bwd2" : "nerfart_volsdf_render_bwd";
+    if (int rc_ = blob_term_check(surf_blob, 1, who)) return rc_;
+    if (int rc_ = blob_term_check(rad_blob, 1, who)) return rc_;
     if (n_rays <= 0) return 0;
     if (int rc = check_rays(n_rays, P, "volsdf_render_bwd")) return rc;
     int mv;
@@ -476,12 +492,16 @@ int nerfart_volsdf_render_bwd(const float* surf_blob, const float* rad_blob, int
     if (!surf_blob || !rad_blob || !rays_o || !rays_d || !d_all || !g_rgb || !raw) { set_last_error("volsdf_render_bwd: null argument"); return 2; }
     const int have_state = sdf_state || nabla_state || h7_state;
     if (have_state && !(sdf_state && nabla_state && h7_state)) { set_last_error("volsdf_render_bwd: pass all of sdf_state / nabla_state / h7_state or none"); return 2; }
-    if (!workspace || workspace_bytes < nerfart_volsdf_render_bwd_workspace_bytes(n_rays, P, have_state)) {
-        set_last_error("volsdf_render_bwd: workspace missing or smaller than nerfart_volsdf_render_bwd_workspace_bytes()"); return 2;
+    const int have_normals = g_normals != nullptr;
+    if (!workspace || workspace_bytes < nerfart_volsdf_render_bwd2_workspace_bytes(n_rays, P, have_state, have_normals)) {
+        set_last_error(geo ? "volsdf_render_bwd2: workspace missing or smaller than nerfart_volsdf_render_bwd2_workspace_bytes()"
+                           : "volsdf_render_bwd: workspace missing or smaller than nerfart_volsdf_render_bwd_workspace_bytes()");
+        return 2;
     }
     hipStream_t st = (hipStream_t)stream;
     Carver c(workspace);
-    VolWs w = carve_volsdf(c, n_rays, P, have_state);
+    float* g_nab = nullptr;
+    VolWs w = carve_volsdf2(c, n_rays, P, have_state, have_normals, &g_nab);
     const long long R = n_rays, M = R * P;
     float* scal = raw + section_offset(S_SCALARS);
     if (int rc = nerfart_normalize_dirs(rays_d, w.dn, n_rays, st)) return rc;
@@ -493,6 +513,11 @@ int nerfart_volsdf_render_bwd(const float* surf_blob, const float* rad_blob, int
     }
     if (int rc = nerfart_radiance_fwd_dump(rad_blob, view_tiles, w.pts, w.view, M, nab, h7, w.rad.rgb, w.rad.dump, st)) return rc;
     if (int rc = nerfart_volsdf_composite_bwd(n_rays, P, d_all, sdf, w.rad.rgb, alpha, beta, white_bkgd, g_rgb, g_acc, w.g_sdf, w.rad.g_rad, scal, st)) return rc;
+    if (geo) {
+        // the depth / normals maps' share: added to g_sdf and to the (alpha, beta) scalars; its nabla cotangent (+ the caller's) replaces g_n_extra
+        if (int rc = nerfart_volsdf_composite_geo_bwd(n_rays, P, d_all, sdf, nab, alpha, beta, g_depth, g_normals, g_n_extra, 1, w.g_sdf, g_nab, scal, st)) return rc;
+        if (have_normals) g_n_extra = g_nab;
+    }
     if (int rc = nerfart_radiance_bwd(rad_blob, M, w.rad.rgb, w.rad.g_rad, w.rad.dump, w.rad.bdump, w.rad.g_h7, w.rad.g_n, st)) return rc;
     // sbar: no gradient to the net where sdf = min(net, R - |x|) took the sphere; nbar = g_n + the eikonal term's gradient
     if (int rc = nerfart_volsdf_pass2_cotangents(w.pts, sdf, w.g_sdf, nab, w.rad.g_n, g_n_extra, R, P, R_bg, w_eikonal, eik_group_rays, w.sbar, w.nbar, w.eik_ray, st)) return rc;
@@ -500,6 +525,16 @@ int nerfart_volsdf_render_bwd(const float* surf_blob, const float* rad_blob, int
     const void* a7 = nullptr;
     if (int rc = surf_param_bwd(surf_blob, multires, w.pts, M, w.sbar, w.rad.g_h7, w.nbar, raw, w.surf, &a7, st)) return rc;
     return rad_param_bwd(mv, w.pts, w.view, nab, M, w.rad.g_rad, a7, train_radiance, raw, w.rad, st);
+}
+
+int nerfart_volsdf_render_bwd(const float* surf_blob, const float* rad_blob, int view_tiles, int multires, const float* rays_o, const float* rays_d,
+                              int n_rays, int P, const float* d_all, const float* g_rgb, const float* g_acc, const float* g_n_extra,
+                              const float* sdf_state, const float* nabla_state, const float* h7_state, float R_bg, float alpha, float beta,
+                              int white_bkgd, float w_eikonal, int eik_group_rays, int train_radiance, float* raw, void* workspace,
+                              long long workspace_bytes, void* stream) {
+    return nerfart_volsdf_render_bwd2(surf_blob, rad_blob, view_tiles, multires, rays_o, rays_d, n_rays, P, d_all, g_rgb, g_acc, g_n_extra, nullptr, nullptr,
+                                      sdf_state, nabla_state, h7_state, R_bg, alpha, beta, white_bkgd, w_eikonal, eik_group_rays, train_radiance, raw,
+                                      workspace, workspace_bytes, stream);
 }
 
 long long nerfart_neus_render_bwd_workspace_bytes(int n_rays, int P, int have_state) {

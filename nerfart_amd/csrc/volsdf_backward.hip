@@ -8,23 +8,12 @@
 //       g_sigma_j = [x_j > 0] delta_j g_x_j;  g_s_j = g_sigma_j alpha dpsi/ds,  dpsi/ds = -e^{-|s|/beta} / (2 beta)
 //       g_alpha += g_sigma_j psi_j;  g_beta += g_sigma_j alpha dpsi/dbeta,  dpsi/dbeta = e^{-|s|/beta} s / (2 beta^2)
 // One wave per ray (P - 1 intervals, in-lane sequential + 64-lane scans), like the forward kernel.  The last
-// sample of a ray carries no weight (volsdf.py:556-560): its cotangents are 0.  Only the rgb cotangent is an
-// input: the reference's losses do not touch depth / mask / normals maps.
+// sample of a ray carries no weight (volsdf.py:556-560): its cotangents are 0.  The rgb cotangent and the opacity
+// cotangent g_acc are the inputs here (all the reference's losses touch); the cotangents of the depth and normals maps go through
+// k_composite_volsdf_geo_bwd (volsdf_geo_backward.hip), which adds its share to the same g_sdf.
 #include "ray_common.h"
 
 namespace nerfart {
-
-// sum over the lanes AFTER this one (lane 63 gets 0)
-__device__ __forceinline__ float wave_excl_suffix_sum(float v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const float t = __shfl_down(v, o, 64);
-        if (lane + o < 64) v += t;
-    }
-    const float e = __shfl_down(v, 1, 64);
-    return lane == 63 ? 0.f : e;
-}
 
 __global__ void __launch_bounds__(64)
 k_composite_volsdf_bwd(int P, const float* __restrict__ d_all, const float* __restrict__ sdf,

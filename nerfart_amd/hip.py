@@ -73,6 +73,7 @@ _SIGS = {
     "nerfart_volsdf_composite": (_i, [_i, _i, _p, _p, _p, _p, _f, _f, _i] + [_p] * 8),
     "nerfart_volsdf_composite_bwd": (_i, [_i, _i, _p, _p, _p, _f, _f, _i, _p, _p, _p, _p, _p, _p]),
     "nerfart_neus_composite_bwd": (_i, [_i, _i, _p, _p, _f, _i, _p, _p, _p, _p, _p, _p]),
+    "nerfart_volsdf_composite_geo_bwd": (_i, [_i, _i, _p, _p, _p, _f, _f, _p, _p, _p, _i, _p, _p, _p, _p]),
     "nerfart_sdf_fwd2_dump_bytes": (_ll, [_ll]),
     "nerfart_sdf_bwd2_dump_bytes": (_ll, [_ll]),
     "nerfart_sdf_fwd2": (_i, [_p, _p, _p, _ll, _p, _p]),
@@ -115,6 +116,8 @@ _SIGS = {
     "nerfart_pass2_raw_layout": (_ll, [_p]),
     "nerfart_volsdf_render_bwd_workspace_bytes": (_ll, [_i, _i, _i]),
     "nerfart_volsdf_render_bwd": (_i, [_p, _p, _i, _i, _p, _p, _i, _i] + [_p] * 7 + [_f, _f, _f, _i, _f, _i, _i, _p, _p, _ll, _p]),
+    "nerfart_volsdf_render_bwd2_workspace_bytes": (_ll, [_i, _i, _i, _i]),
+    "nerfart_volsdf_render_bwd2": (_i, [_p, _p, _i, _i, _p, _p, _i, _i] + [_p] * 9 + [_f, _f, _f, _i, _f, _i, _i, _p, _p, _ll, _p]),
     "nerfart_neus_render_bwd_workspace_bytes": (_ll, [_i, _i, _i]),
     "nerfart_neus_render_bwd": (_i, [_p, _p, _i, _i, _p, _p, _i, _i] + [_p] * 5 + [_f, _i, _f, _i, _i, _p, _p, _ll, _p]),
     "nerfart_sdf_param_bwd_workspace_bytes": (_ll, [_ll]),
@@ -683,17 +686,19 @@ def radiance_bwd(rad_blob, rgb, g_rgb, fwd_dump):
     return g_h7, g_n, bwd_dump
 
 
-def volsdf_composite(d_all, sdf, radiance, alpha: float, beta: float, white_bkgd: bool = False):
-    """rgb [R,3], depth [R], acc [R] of nerfart_volsdf_composite for d_all / sdf [R,P], radiance [R,P,3]."""
+def volsdf_composite(d_all, sdf, radiance, alpha: float, beta: float, white_bkgd: bool = False, nabla=None):
+    """rgb [R,3], depth [R], acc [R] of nerfart_volsdf_composite for d_all / sdf [R,P], radiance [R,P,3]; with nabla [R,P,3] also normals [R,3]
+    (a 4-tuple)."""
     R, P = d_all.shape
     dev = d_all.device
     rgb = torch.empty(R, 3, dtype=torch.float32, device=dev)
     depth = torch.empty(R, dtype=torch.float32, device=dev)
     acc = torch.empty(R, dtype=torch.float32, device=dev)
-    _check(lib.nerfart_volsdf_composite(R, P, _dev(d_all), _dev(sdf), _dev(radiance), None, float(alpha), float(beta),
-                                        int(bool(white_bkgd)), _dev(rgb), _dev(depth), _dev(acc), None, None, None, None, _stream()),
+    normals = None if nabla is None else torch.empty(R, 3, dtype=torch.float32, device=dev)
+    _check(lib.nerfart_volsdf_composite(R, P, _dev(d_all), _dev(sdf), _dev(radiance), _dev(nabla, name="nabla"), float(alpha), float(beta),
+                                        int(bool(white_bkgd)), _dev(rgb), _dev(depth), _dev(acc), _dev(normals), None, None, None, _stream()),
            "nerfart_volsdf_composite")
-    return rgb, depth, acc
+    return (rgb, depth, acc) if nabla is None else (rgb, depth, acc, normals)
 
 
 def volsdf_composite_bwd(d_all, sdf, radiance, alpha: float, beta: float, g_rgb, white_bkgd: bool = False, g_acc=None):
@@ -708,6 +713,29 @@ def volsdf_composite_bwd(d_all, sdf, radiance, alpha: float, beta: float, g_rgb,
                                             int(bool(white_bkgd)), _dev(g_rgb), _dev(g_acc, name="g_acc"), _dev(g_sdf), _dev(g_rad), _dev(g_ab),
                                             _stream()), "nerfart_volsdf_composite_bwd")
     return g_sdf, g_rad, g_ab
+
+
+def volsdf_composite_geo_bwd(d_all, sdf, alpha: float, beta: float, g_depth=None, g_normals=None, nabla=None, g_n_in=None, g_sdf=None,
+                             g_nabla=None, g_alpha_beta=None, accumulate: bool = False):
+    """nerfart_volsdf_composite_geo_bwd: the cotangents of the depth map (g_depth [R]) and of the normals map (g_normals [R,3], needs nabla [R,P,3]) of
+    the VolSDF compositor -> (g_sdf [R,P], g_nabla [R,P,3] or None, g_alpha_beta [2]).  g_sdf / g_nabla / g_alpha_beta: the caller's buffers (g_sdf is
+    added to when `accumulate`, g_alpha_beta always); None: fresh ones (g_alpha_beta zeroed).  g_n_in [R,P,3]: added into g_nabla.  A depth cotangent on
+    an empty ray is amplified by 1 / (acc + 1e-10), as in the reference's autograd: weight it with the opacity."""
+    R, P = d_all.shape
+    dev = d_all.device
+    if g_sdf is None:
+        if accumulate:
+            raise ValueError("volsdf_composite_geo_bwd: accumulate=True needs the g_sdf to add to")
+        g_sdf = torch.empty(R, P, dtype=torch.float32, device=dev)
+    if g_nabla is None and g_normals is not None:
+        g_nabla = torch.empty(R, P, 3, dtype=torch.float32, device=dev)
+    if g_alpha_beta is None:
+        g_alpha_beta = torch.zeros(2, dtype=torch.float32, device=dev)
+    _check(lib.nerfart_volsdf_composite_geo_bwd(R, P, _dev(d_all, name="d_all"), _dev(sdf, name="sdf"), _dev(nabla, name="nabla"), float(alpha), float(beta),
+                                                _dev(g_depth, name="g_depth"), _dev(g_normals, name="g_normals"), _dev(g_n_in, name="g_n_in"),
+                                                int(bool(accumulate)), _dev(g_sdf, name="g_sdf"), _dev(g_nabla, name="g_nabla"),
+                                                _dev(g_alpha_beta, name="g_alpha_beta"), _stream()), "nerfart_volsdf_composite_geo_bwd")
+    return g_sdf, (g_nabla if g_normals is not None else None), g_alpha_beta
 
 
 def neus_composite_bwd(sdf, rad_mid, s: float, g_rgb, white_bkgd: bool = False, g_acc=None):
@@ -742,20 +770,33 @@ def new_raw(device) -> torch.Tensor:
 
 def volsdf_render_bwd(surf_blob, rad_blob, view_tiles: int, multires: int, rays_o, rays_d, d_all, g_rgb, raw, *, R_bg: float, alpha: float,
                       beta: float, white_bkgd: bool = False, w_eikonal: float = 0.0, eik_group_rays: int = 0, train_radiance: bool = True,
-                      g_acc=None, g_n_extra=None, state=None):
+                      g_acc=None, g_n_extra=None, state=None, g_depth=None, g_normals=None):
     """rgb.backward(g_rgb) + eikonal.backward() of one launch group of VolSDF rays (volsdf.py:759-770) -> accumulated into `raw`.
-    rays_d un-normalised; d_all [R, P] from pass 1; state = (sdf [R P], nabla [R P, 3], h7 [R P, 256]) kept from pass 1 or None."""
+    rays_d un-normalised; d_all [R, P] from pass 1; state = (sdf [R P], nabla [R P, 3], h7 [R P, 256]) kept from pass 1 or None.
+    g_depth [R] / g_normals [R, 3]: cotangents of the depth and normals maps (nerfart_volsdf_render_bwd2; either given selects that entry point)."""
     R, P = d_all.shape
-    need_term(surf_blob, "bf16", "nerfart_volsdf_render_bwd"); need_term(rad_blob, "bf16", "nerfart_volsdf_render_bwd")
     sdf, nab, h7 = state if state is not None else (None, None, None)
-    nb = int(lib.nerfart_volsdf_render_bwd_workspace_bytes(R, P, int(state is not None)))
+    if g_depth is None and g_normals is None:
+        need_term(surf_blob, "bf16", "nerfart_volsdf_render_bwd"); need_term(rad_blob, "bf16", "nerfart_volsdf_render_bwd")
+        nb = int(lib.nerfart_volsdf_render_bwd_workspace_bytes(R, P, int(state is not None)))
+        ws = _workspace(nb, d_all.device)
+        _check(lib.nerfart_volsdf_render_bwd(
+            _dev(surf_blob), _dev(rad_blob), int(view_tiles), int(multires), _dev(rays_o, name="rays_o"), _dev(rays_d, name="rays_d"), R, P,
+            _dev(d_all, name="d_all"), _dev(g_rgb, name="g_rgb"), _dev(g_acc, name="g_acc"), _dev(g_n_extra, name="g_n_extra"),
+            _dev(sdf, name="sdf_state"), _dev(nab, name="nabla_state"), _dev(h7, name="h7_state"), float(R_bg), float(alpha), float(beta),
+            int(bool(white_bkgd)), float(w_eikonal), int(eik_group_rays or 0), int(bool(train_radiance)), _dev(raw, name="raw"), ws.data_ptr(),
+            ws.numel(), _stream()), "nerfart_volsdf_render_bwd")
+        return
+    need_term(surf_blob, "bf16", "nerfart_volsdf_render_bwd2"); need_term(rad_blob, "bf16", "nerfart_volsdf_render_bwd2")
+    nb = int(lib.nerfart_volsdf_render_bwd2_workspace_bytes(R, P, int(state is not None), int(g_normals is not None)))
     ws = _workspace(nb, d_all.device)
-    _check(lib.nerfart_volsdf_render_bwd(
+    _check(lib.nerfart_volsdf_render_bwd2(
         _dev(surf_blob), _dev(rad_blob), int(view_tiles), int(multires), _dev(rays_o, name="rays_o"), _dev(rays_d, name="rays_d"), R, P,
         _dev(d_all, name="d_all"), _dev(g_rgb, name="g_rgb"), _dev(g_acc, name="g_acc"), _dev(g_n_extra, name="g_n_extra"),
+        _dev(g_depth, name="g_depth"), _dev(g_normals, name="g_normals"),
         _dev(sdf, name="sdf_state"), _dev(nab, name="nabla_state"), _dev(h7, name="h7_state"), float(R_bg), float(alpha), float(beta),
         int(bool(white_bkgd)), float(w_eikonal), int(eik_group_rays or 0), int(bool(train_radiance)), _dev(raw, name="raw"), ws.data_ptr(),
-        ws.numel(), _stream()), "nerfart_volsdf_render_bwd")
+        ws.numel(), _stream()), "nerfart_volsdf_render_bwd2")
 
 
 def neus_render_bwd(surf_blob, rad_blob, view_tiles: int, multires: int, rays_o, rays_d, d_all, g_rgb, raw, *, s: float, white_bkgd: bool = False,

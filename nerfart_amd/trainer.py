@@ -83,6 +83,8 @@ class Trainer(nn.Module):
         # 67,200 rays per sampler batch, about half the fused renderer's 131,072-ray chunk (measured: 4 -> 14 takes 8 ms off a 480 x 270 step)
         self.pass1_groups = max(1, pass1_groups)
         self._kept = None
+        # finetune_step(geometry_loss=...): pass 1 also leaves every launch's (depth [n], normals [n, 3], mask [n]) maps here, in ray order; None: not wanted
+        self._maps = None
         # neus.py:455-456: NeuS fine-tuning trains only the SDF net (and ln_s); pass freeze_radiance=False for the
         # reconstruction objective (reconstruction_step), which trains everything
         if self.is_neus if freeze_radiance is None else freeze_radiance:
@@ -179,6 +181,8 @@ class Trainer(nn.Module):
             n = rays_o.reshape(-1, 3).shape[0]
             kw["uniforms"] = self._uniform(1, 0, n, ra.N_importance, rays_o.device)
         rgb, depth, extras = render_fn(rays_o, rays_d, detailed_output=want_depths, require_nablas=True, calc_normal=True, **kw)
+        if self._maps is not None:
+            self._maps.append((depth.reshape(-1), extras["normals_volume"].reshape(-1, 3), extras["mask_volume"].reshape(-1)))
         if want_depths:
             d = extras["d_all" if self.is_neus else "d_vals"]
             return rgb, d.reshape(-1, d.shape[-1])
@@ -222,6 +226,11 @@ class Trainer(nn.Module):
         pts, v = hip.ray_points(o, dn, depths)
         sdf, nab, h7 = hip.sdf_nabla_fwd(surf_blob, pts, m.obj_bounding_radius, precision=m.precision_id)
         rgb_pt = hip.radiance_fwd(rad_blob, m.view_tiles, pts, v, nab, h7, precision=m.precision_id)
+        if self._maps is not None:                             # the geometry maps from the same composite call (its normals output)
+            rgb, depth, acc, normals = hip.volsdf_composite(depths, sdf.reshape(-1, ra.P), rgb_pt.reshape(-1, ra.P, 3), ab[0], ab[1], ra.white_bkgd,
+                                                            nabla=nab.reshape(-1, ra.P, 3))
+            self._maps.append((depth, normals, acc))
+            return rgb, sdf, nab, h7
         rgb, _, _ = hip.volsdf_composite(depths, sdf.reshape(-1, ra.P), rgb_pt.reshape(-1, ra.P, 3), ab[0], ab[1], ra.white_bkgd)
         return rgb, sdf, nab, h7
 
@@ -297,16 +306,26 @@ class Trainer(nn.Module):
             raise RuntimeError("render_two_draws feeds the native pass 2: set_precision('mixed') or ('bf16x3') first")
         return self._staged_pass1(rays_o, rays_d, rk, two_draws=True)
 
-    def backward_patches(self, rays_o, rays_d, gradient, depths_all=None, kept=None, **render_kwargs):
+    def backward_patches(self, rays_o, rays_d, gradient, depths_all=None, kept=None, gradient_depth=None, gradient_normals=None, gradient_mask=None,
+                         **render_kwargs):
         """Pass 2: accumulates parameter gradients for d loss / d rgb = `gradient` [N, 3] (+ the eikonal term).
         depths_all [N, P]: sample depths from pass 1 (skips the re-sampling); kept: render_keep's per-group state of
         exactly these rays (skips the SDF re-evaluation too).  Returns the mean eikonal loss over the reference's
-        pass2_rays-ray patches (what the reference prints)."""
+        pass2_rays-ray patches (what the reference prints).
+        gradient_depth [N] / gradient_normals [N, 3] / gradient_mask [N]: d loss / d depth_volume, normals_volume, mask_volume - the geometry terms of
+        an objective (VolSDF only; native: k_composite_volsdf_geo_bwd inside nerfart_volsdf_render_bwd2, and g_acc).  A depth cotangent on a ray that
+        hits nothing is amplified by 1 / (mask_volume + 1e-10), as autograd through the reference amplifies it: weight it with the mask."""
         self._training_sampler()
         o_all = rays_o.reshape(-1, 3).float().contiguous()
         d_all_ = rays_d.reshape(-1, 3).float().contiguous()
         g_all = gradient.reshape(-1, 3)
         N = o_all.shape[0]
+        geo = [None if t is None else t.detach().reshape(N, *shp).float() for t, shp in ((gradient_depth, ()), (gradient_normals, (3,)), (gradient_mask, ()))]
+        have_geo = any(t is not None for t in geo)
+        if have_geo and self.is_neus:
+            raise NotImplementedError("backward_patches: gradient_depth / gradient_normals / gradient_mask (the geometry-map cotangents) are "
+                                      "implemented for VolSDF only")
+        cut = lambda t, a, b: None if t is None else t[a:b].contiguous()
         ra = self._render_args(render_kwargs)
         eik_sum, n = 0.0, 0
         if self.native:
@@ -346,7 +365,8 @@ class Trainer(nn.Module):
                                                                 s_val=s_val, accum=accum, eik_group_rays=self.pass2_rays, state=state)
                 else:
                     eik = autodiff.volsdf_backward_samples_native(self.model, o, d_raw, depths, g, self.w_eikonal, self.use_eikonal, ra.white_bkgd,
-                                                                  ab=ab, accum=accum, state=state, eik_group_rays=self.pass2_rays)
+                                                                  ab=ab, accum=accum, state=state, eik_group_rays=self.pass2_rays,
+                                                                  g_depth=cut(geo[0], i0, i1), g_normals=cut(geo[1], i0, i1), g_acc=cut(geo[2], i0, i1))
                 eik_sum = eik_sum + eik
                 n += -(-(i1 - i0) // self.pass2_rays)
                 del state
@@ -357,17 +377,25 @@ class Trainer(nn.Module):
             dn = F.normalize(d_raw, dim=-1)
             with torch.no_grad():
                 depths = self._samples(o, dn, d_raw, render_kwargs, 2, i) if depths_all is None else depths_all[i:i + self.pass2_rays].contiguous()
-            fn = autodiff.neus_render_samples if self.is_neus else autodiff.volsdf_render_samples
-            out = fn(self.model, o, dn, depths, white_bkgd=ra.white_bkgd)
+            if have_geo:
+                # the native compositor of a GPU run yields rgb only: the maps need the torch formulation of the per-ray stage
+                out = autodiff.volsdf_render_samples(self.model, o, dn, depths, white_bkgd=ra.white_bkgd, native_composite=False)
+            else:
+                fn = autodiff.neus_render_samples if self.is_neus else autodiff.volsdf_render_samples
+                out = fn(self.model, o, dn, depths, white_bkgd=ra.white_bkgd)
+            tensors, grads = [out["rgb"]], [g_all[i:i + self.pass2_rays]]
+            for key, t in zip(("depth_volume", "normals_volume", "mask_volume"), geo):
+                if t is not None:
+                    tensors.append(out[key]); grads.append(t[i:i + self.pass2_rays])
             if self.use_eikonal:
                 # the reference calls rgb.backward(g, retain_graph=True) and then eikonal.backward(): the same sum of
                 # gradients from ONE traversal of the (double-backward) graph of the SDF net
                 nn_ = out["implicit_nablas"].reshape(-1, 3).norm(dim=-1)
                 eik = self.w_eikonal * F.mse_loss(nn_, torch.ones_like(nn_), reduction="mean")
-                torch.autograd.backward([out["rgb"], eik], [g_all[i:i + self.pass2_rays], torch.ones_like(eik)])
+                torch.autograd.backward(tensors + [eik], grads + [torch.ones_like(eik)])
                 eik_sum += float(eik.detach())
             else:
-                out["rgb"].backward(g_all[i:i + self.pass2_rays])
+                torch.autograd.backward(tensors, grads)
             n += 1
             del out
         return float(eik_sum) / max(n, 1)
@@ -565,9 +593,15 @@ class Trainer(nn.Module):
         return rgb.reshape(-1, 3), depths
 
     # ---- one fine-tune step ---------------------------------------------------------------------------
-    def finetune_step(self, render_fn, rays_o, rays_d, target_rgb, H: int, style_loss, optimizer=None, tile: int = None,
+    def finetune_step(self, render_fn, rays_o, rays_d, target_rgb, H: int, style_loss, optimizer=None, tile: int = None, geometry_loss=None,
                       **render_kwargs):
         """style_loss(rgb_pred [B,3,H,W], rgb_gt [B,3,H,W]) -> scalar.  Returns dict(loss, eikonal, rgb).
+
+        geometry_loss (VolSDF, single process): a callable that gets pass 1's maps as leaf tensors - {"depth": [1,1,H,W], "normals": [1,3,H,W],
+        "mask": [1,1,H,W]} - and returns a scalar that is added to the style loss (depth preservation, normal consistency, smoothness ...); the maps'
+        .grad go to backward_patches(gradient_depth=, gradient_normals=, gradient_mask=) and the returned dict gains "geometry".  The depth of a ray
+        that hits nothing is a quotient by mask + 1e-10 and its cotangent is amplified accordingly: weight depth terms with the mask.  None: the step
+        is exactly the step without this argument.
 
         With torch.distributed initialised (one process per GPU) the step is ray-parallel: pass 1
         renders this rank's tiles and all-gathers the image; every rank evaluates the (cheap, deterministic) style
@@ -582,7 +616,13 @@ class Trainer(nn.Module):
         resample = self.resamples(render_kwargs)           # pass 2 draws its own samples (the reference under perturb=True)
         keep = self.native and not resample                # pass 1 keeps its per-point state for pass 2 (render_keep)
         share = self.shares_algorithm1(render_kwargs)      # ... from the SAME run of Algorithm 1 (VolSDF: render_two_draws)
-        self._kept = self._depths2 = None
+        self._kept = self._depths2 = self._maps = None
+        if geometry_loss is not None:
+            if self.is_neus:
+                raise NotImplementedError("finetune_step: geometry_loss (losses on the depth / normals / mask maps) is implemented for VolSDF only")
+            if sharded:
+                raise NotImplementedError("finetune_step: geometry_loss is not implemented for the ray-sharded step (torch.distributed)")
+            self._maps = []
         if sharded:
             kw = {k: v for k, v in render_kwargs.items() if k != "rayschunk"}
             n_frame = rays_o.reshape(-1, 3).shape[0]
@@ -601,8 +641,21 @@ class Trainer(nn.Module):
         W = rgb.shape[1] // H
         to_img = lambda t: t.reshape(t.shape[0], H, W, 3).permute(0, 3, 1, 2)          # "B (H W) C -> B C H W"
         loss = style_loss(to_img(rgb), to_img(target_rgb.reshape(1, -1, 3)))
+        geo_grads, geo_value = {}, None
+        if geometry_loss is not None:
+            maps_in, self._maps = self._maps, None
+            to_map = lambda parts, c: torch.cat(parts, 0).detach().reshape(1, H, W, c).permute(0, 3, 1, 2).contiguous().requires_grad_(True)
+            maps = {"depth": to_map([m[0] for m in maps_in], 1), "normals": to_map([m[1] for m in maps_in], 3), "mask": to_map([m[2] for m in maps_in], 1)}
+            geo = geometry_loss(maps)
+            geo_value = float(geo.detach())
+            loss = loss + geo
         loss.backward()
         gradient = rgb.grad.detach()
+        if geometry_loss is not None:
+            # a map the loss did not touch has no cotangent: it is not passed on
+            flat = lambda t: None if t.grad is None else t.grad.detach().permute(0, 2, 3, 1).reshape(H * W, -1)
+            gd, gn, gm = flat(maps["depth"]), flat(maps["normals"]), flat(maps["mask"])
+            geo_grads = dict(gradient_depth=None if gd is None else gd.reshape(-1), gradient_normals=gn, gradient_mask=None if gm is None else gm.reshape(-1))
         if optimizer is not None:
             optimizer.zero_grad()
         if sharded:
@@ -615,9 +668,12 @@ class Trainer(nn.Module):
                     p.grad = torch.zeros_like(p)
             nd.allreduce_gradients([p for p in self.model.parameters() if p.requires_grad])
         else:
-            eik = self.backward_patches(rays_o, rays_d, gradient[0], depths_all=depths_all, kept=self._kept, **render_kwargs)
+            eik = self.backward_patches(rays_o, rays_d, gradient[0], depths_all=depths_all, kept=self._kept, **geo_grads, **render_kwargs)
         self._kept = self._depths2 = self._global_rays = None
-        return {"loss": float(loss.detach()), "eikonal": eik, "rgb": rgb.detach()}
+        out = {"loss": float(loss.detach()), "eikonal": eik, "rgb": rgb.detach()}
+        if geo_value is not None:
+            out["geometry"] = geo_value
+        return out
 
 
 class _DeferredBackward(torch.autograd.Function):
