@@ -364,9 +364,47 @@ int nerfart_neus_render_algo_fwd(const float* surf_blob, const float* rad_blob, 
  *   workspace : nerfart_clip_vitb32_workspace_bytes(B, keep_for_bwd) bytes of device memory.  With keep_for_bwd != 0 the
  *               forward leaves the per-block activations there and nerfart_clip_vitb32_image_bwd(g_feat [B,512] ->
  *               g_img [B,3,224,224]) must be given the SAME workspace, untouched; several forwards may be outstanding,
- *               each with its own workspace. */
+ *               each with its own workspace.
+ *
+ * nerfart_clip_vitb32_workspace_layout (host arithmetic only) returns the same total as nerfart_clip_vitb32_workspace_bytes (0 for B < 1) and, with
+ * offsets != NULL, the byte offsets of the workspace's buffers, offsets[21] (each a multiple of 256), in this order.  M = 50 B token rows (row
+ * b 50 + t: t = 0 the class token, t >= 1 patch t - 1), P = 49 B patch rows; Mp, Pp, Bp = M, P, B rounded up to 64 (the GEMM tile).  Every
+ * buffer is row-major with the row stride of its logical width; rows past the logical count are padding the kernels never store.
+ *    0 scale   fp32 [2]            backward: s, the power of two the cotangent is multiplied by, and 1 / s.  s = min(2^floor(log2(16 / max|g_feat|)),
+ *                                  2^126), 1 for an all-zero g_feat or a non-finite max-abs (a non-finite g_feat gives a non-finite g_img)
+ *    1 patches fp16 [P, 3072]  Pp  forward: the image's patches, column c 1024 + kh 32 + kw
+ *    2 pe      fp32 [P, 768]   Pp  forward: patches . conv1^T;  after a backward to stop_layer 0: fp32 [P, 3072] s d patches (the buffer has
+ *                                  Pp x 3072 floats)
+ *    3 xemb    fp32 [M, 768]   Mp  forward: class / patch embedding + positional embedding (ln_pre's input)
+ *    4 xfin    fp32 [M, 768]   Mp  forward: the residual stream after block 11
+ *    5 y       fp16 [M, 768]   Mp  forward: the last LayerNorm output (ln_2 of block 11);  after a backward to 0: fp16 [P, 768] (Pp rows)
+ *                                  s d patch embedding
+ *    6 att     fp16 [M, 768]   Mp  forward: block 11's attention output (heads side by side);  backward: the last block run's d of that
+ *    7 act     fp16 [M, 3072]  Mp  forward: block 11's QuickGELU output;  backward: the last block run's d pre-activation (d act . gelu'(pre))
+ *    8 t       fp32 [M, 768]   Mp  backward only: the last block run's d ln_1 output (dqkv . in_proj)
+ *    9 dx      fp32 [M, 768]   Mp  backward only: s d residual stream entering the last block run, from above (= d xin of that block)
+ *   10 dqkv    fp16 [M, 2304]  Mp  backward only: the last block run's d qkv
+ *   11 x0      fp16 [B, 768]   Bp  forward: ln_post of the class rows
+ *   12 g16     fp16 [B, 512]   Bp  backward: fp16(s g_feat)
+ *   13 t0      fp32 [B, 768]   Bp  backward: g16 . proj^T
+ *   14 saved   the per-block buffers: block l at saved + l layer_bytes with keep_for_bwd != 0; with 0 one block reused by all, followed by
+ *              an fp32 [Mp, 768] buffer the residual stream ping-pongs through
+ *   15 layer_bytes (a size, not an offset)
+ *   16 xin  fp32 [M, 768]   17 xmid  fp32 [M, 768] (after the attention branch)   18 qkv  fp16 [M, 2304] (q | k | v, head h at columns
+ *   64 h)   19 pre  fp16 [M, 3072] (c_fc output before QuickGELU) - offsets inside a block, Mp rows each
+ *   20 total
+ * The forward zeroes [0, saved) (everything with keep_for_bwd == 0); the padding rows of the saved blocks keep the caller's bytes: they are read
+ * as GEMM / LayerNorm operands of padding rows only, whose results are never stored.
+ *
+ * nerfart_clip_vitb32_image_bwd_partial is the backward with its block loop ending at stop_layer (0 .. 12, else refused before any launch): the
+ * head (scale, g16, t0, the class rows of dx), blocks 11 .. stop_layer, and only for stop_layer == 0 the tail (y, d patches, g_img) - with 0 it IS
+ * nerfart_clip_vitb32_image_bwd.  For stop_layer > 0 g_img may be NULL and is never touched.  No kernel uses atomics: runs on the same saved
+ * forward repeat bit for bit, so a run to l + 1 and a run to l give block l's incoming dx and everything block l leaves (tests). */
 long long nerfart_clip_vitb32_blob_layout(long long* offsets);
 long long nerfart_clip_vitb32_workspace_bytes(int B, int keep_for_bwd);
+long long nerfart_clip_vitb32_workspace_layout(int B, int keep_for_bwd, long long* offsets);
+int nerfart_clip_vitb32_image_bwd_partial(const void* blob, long long blob_bytes, int B, const float* g_feat, float* g_img, void* workspace,
+                                          long long workspace_bytes, int stop_layer, void* stream);
 int nerfart_clip_vitb32_image_fwd(const void* blob, long long blob_bytes, const float* img, int B, float* feat_out, int keep_for_bwd, void* workspace,
                                   long long workspace_bytes, void* stream);
 int nerfart_clip_vitb32_image_bwd(const void* blob, long long blob_bytes, int B, const float* g_feat, float* g_img, void* workspace, long long workspace_bytes,

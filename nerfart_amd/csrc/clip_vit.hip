@@ -239,7 +239,9 @@ __global__ __launch_bounds__(256) void k_lnpost_bwd(const float* __restrict__ t0
     const Row d = row_ln_bwd(row_load(t0 + (size_t)b * D, lane), row_load(x + (size_t)b * L * D, lane), g, lane);
     row_store_f32(dx + (size_t)b * L * D, d, lane, false);
 }
-// scale[0] = s = 2^floor(log2(16 / max|g|)) (1 if g == 0), scale[1] = 1 / s;  g16 = fp16(g s), [B, 512] (one workgroup)
+// scale[0] = s = min(2^floor(log2(16 / max|g|)), 2^126) (1 if g == 0 or max|g| is not finite), scale[1] = 1 / s;  g16 = fp16(g s), [B, 512]
+// (one workgroup).  The clamp: 16 / m overflows for m < 2^-124 (every subnormal m among them) and s = inf made g16 inf / NaN; 2^126 keeps s and
+// 1 / s normal numbers, and such a cotangent simply arrives smaller than 16 in fp16 (the chain is linear).
 __global__ __launch_bounds__(1024) void k_gscale(const float* __restrict__ g, int n, float* __restrict__ scale, half_t* __restrict__ g16) {
     __shared__ float red[16];
     float m = 0.f;
@@ -251,7 +253,7 @@ __global__ __launch_bounds__(1024) void k_gscale(const float* __restrict__ g, in
     m = red[0];
 #pragma unroll
     for (int i = 1; i < 16; ++i) m = fmaxf(m, red[i]);
-    const float s = (m > 0.f && isfinite(m)) ? exp2f(floorf(log2f(16.0f / m))) : 1.0f;
+    const float s = (m > 0.f && isfinite(m)) ? fminf(exp2f(floorf(log2f(16.0f / m))), 0x1p126f) : 1.0f;
     if (threadIdx.x == 0) { scale[0] = s; scale[1] = 1.0f / s; }
     for (int i = threadIdx.x; i < n; i += 1024) g16[i] = (half_t)(g[i] * s);
 }
@@ -514,6 +516,19 @@ int nerfart_clip_vitb32_pack(const float* const* tensors, void* blob, long long 
 }
 long long nerfart_clip_vitb32_workspace_bytes(int B, int keep_for_bwd) { return B >= 1 ? work_layout(B, keep_for_bwd).total : 0; }
 
+// Host arithmetic only: the byte offsets of the Work buffers (include/nerfart_hip.h documents each one) -> offsets[21], in the order
+// scale, patches, pe, xemb, xfin, y, att, act, t, dx, dqkv, x0, g16, t0, saved, layer_bytes, xin, xmid, qkv, pre, total.
+long long nerfart_clip_vitb32_workspace_layout(int B, int keep_for_bwd, long long* offsets) {
+    if (B < 1) return 0;
+    const Work w = work_layout(B, keep_for_bwd);
+    if (offsets) {
+        const long long o[21] = {w.o_scale, w.o_patches, w.o_pe, w.o_xemb, w.o_xfin, w.o_y, w.o_att, w.o_act, w.o_t, w.o_dx, w.o_dqkv, w.o_x0, w.o_g16, w.o_t0,
+                                 w.o_saved, w.layer_bytes, w.o_xin, w.o_xmid, w.o_qkv, w.o_pre, w.total};
+        for (int i = 0; i < 21; ++i) offsets[i] = o[i];
+    }
+    return w.total;
+}
+
 // C[M, N] fp32 = A[M, K] fp16 . W[N, K]^T fp16 (fp32 accumulate): the GEMM kernel on its own (tests).  M, N, K multiples of 64.
 int nerfart_gemm_f16_nt(const void* A, const void* W, int M, int N, int K, float* C, void* stream) {
     if ((M | N | K) & 63) { set_last_error("nerfart_gemm_f16_nt: M, N, K must be multiples of 64"); return 1; }
@@ -586,9 +601,13 @@ int nerfart_clip_vitb32_image_fwd(const void* blob, long long blob_bytes, const 
     return 0;
 }
 
-int nerfart_clip_vitb32_image_bwd(const void* blob, long long blob_bytes, int B, const float* g_feat, float* g_img, void* workspace, long long workspace_bytes,
-                                  void* stream) {
+// The backward with its block loop ending at stop_layer: the head (gscale, proj^T, ln_post backward), blocks 11 .. stop_layer, and - only for
+// stop_layer == 0 - the tail (ln_pre backward, conv^T, unpatchify).  The scratch buffers keep what the last block run left (tests read them).
+int nerfart_clip_vitb32_image_bwd_partial(const void* blob, long long blob_bytes, int B, const float* g_feat, float* g_img, void* workspace,
+                                          long long workspace_bytes, int stop_layer, void* stream) {
     if (check_args(blob, workspace, B, workspace_bytes, 1) || check_blob_bytes(blob_bytes)) return 1;
+    if (stop_layer < 0 || stop_layer > NL) { set_last_error("clip_vitb32_image_bwd_partial: stop_layer must be in 0..12"); return 1; }
+    if (g_feat == nullptr || (stop_layer == 0 && g_img == nullptr)) { set_last_error("clip_vitb32_image_bwd: null g_feat / g_img"); return 1; }
     hipStream_t st = (hipStream_t)stream;
     Blob bl;
     bl.base = (const char*)blob;
@@ -620,7 +639,7 @@ int nerfart_clip_vitb32_image_bwd(const void* blob, long long blob_bytes, int B,
     { Epi e{}; e.out_f32 = t0; e.ldo = D; e.m_valid = B;
       if (gemm<EPI_F32, A_F16>(st, g16, DOUT, bl.h(99), w.Bp, D, DOUT, e)) return 1; }
     hipLaunchKernelGGL(k_lnpost_bwd, dim3((B + 3) / 4), dim3(256), 0, st, t0, xfin, bl.f(200), dx, B);
-    for (int l = NL - 1; l >= 0; --l) {
+    for (int l = NL - 1; l >= stop_layer; --l) {
         char* lb = ws + w.o_saved + (long long)l * w.layer_bytes;
         const float* xin = (const float*)(lb + w.o_xin);
         const float* xmid = (const float*)(lb + w.o_xmid);
@@ -641,6 +660,7 @@ int nerfart_clip_vitb32_image_bwd(const void* blob, long long blob_bytes, int B,
           if (gemm<EPI_F32, A_F16, true>(st, dqkv, 3 * D, bl.h(s + 0), Mp, D, 3 * D, e)) return 1; }
         hipLaunchKernelGGL(k_ln_bwd, dim3(rows4), dim3(256), 0, st, t, xin, bl.f(f + 0), dx, M);
     }
+    if (stop_layer > 0) { NERFART_HIP(hipGetLastError()); return 0; }
     NERFART_HIP(hipMemsetAsync(y, 0, (size_t)2 * Mp * D, st));
     hipLaunchKernelGGL(k_lnpre_bwd, dim3(rows4), dim3(256), 0, st, dx, xemb, bl.f(102), y, M);
     { Epi e{}; e.out_f32 = dpatch; e.ldo = PK; e.m_valid = B * NP;
@@ -648,6 +668,11 @@ int nerfart_clip_vitb32_image_bwd(const void* blob, long long blob_bytes, int B,
     hipLaunchKernelGGL(k_unpatchify, dim3(B * NP), dim3(256), 0, st, dpatch, scale, g_img, B);
     NERFART_HIP(hipGetLastError());
     return 0;
+}
+
+int nerfart_clip_vitb32_image_bwd(const void* blob, long long blob_bytes, int B, const float* g_feat, float* g_img, void* workspace, long long workspace_bytes,
+                                  void* stream) {
+    return nerfart_clip_vitb32_image_bwd_partial(blob, blob_bytes, B, g_feat, g_img, workspace, workspace_bytes, 0, stream);
 }
 
 }  // extern "C"

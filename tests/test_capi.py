@@ -72,6 +72,25 @@ def test_new_entry_points_validate_their_arguments_without_a_gpu():
     assert lib.nerfart_clip_vitb32_image_fwd(null, 0, null, 4, null, 1, null, 0, null) != 0 and "null" in err()
     assert lib.nerfart_clip_vitb32_workspace_bytes(0, 1) == 0
     assert lib.nerfart_clip_vitb32_workspace_bytes(16, 1) > 12 * 16 * 50 * 768 * 4
+    # the workspace's buffers (host arithmetic only) and the partial backward's refusals, before any launch
+    co = (C.c_longlong * 21)()
+    for keep in (0, 1):
+        ctotal = lib.nerfart_clip_vitb32_workspace_layout(3, keep, C.cast(co, C.c_void_p))
+        assert ctotal == co[20] == lib.nerfart_clip_vitb32_workspace_bytes(3, keep) == lib.nerfart_clip_vitb32_workspace_layout(3, keep, null)
+        assert list(co[:15]) == sorted(co[:15]) and co[0] == 0 and co[1] == 256 and all(v % 256 == 0 for v in co)
+        assert co[2] - co[1] == 2 * 192 * 3072 and co[3] - co[2] == 4 * 192 * 3072 and co[9] - co[8] == 4 * 192 * 768 and co[16] == 0
+        assert co[15] == co[19] + 2 * 192 * 3072 and ctotal == co[14] + (12 * co[15] if keep else co[15] + 4 * 192 * 768)
+    assert lib.nerfart_clip_vitb32_workspace_layout(0, 1, null) == 0 == lib.nerfart_clip_vitb32_workspace_layout(0, 1, C.cast(co, C.c_void_p))
+    assert lib.nerfart_clip_vitb32_image_bwd_partial(null, 0, 1, null, null, null, 0, 0, null) != 0 and "null" in err()
+    one_ = C.c_void_p(16)                                          # non-null, never dereferenced: the checks come first
+    n1 = lib.nerfart_clip_vitb32_workspace_bytes(1, 1)
+    nb = lib.nerfart_clip_vitb32_blob_layout(null)
+    for bad in (-1, 13):
+        assert lib.nerfart_clip_vitb32_image_bwd_partial(one_, nb, 1, one_, one_, one_, n1, bad, null) != 0 and "stop_layer" in err()
+    assert lib.nerfart_clip_vitb32_image_bwd_partial(one_, nb, 1, one_, one_, one_, n1 - 1, 12, null) != 0 and "workspace too small" in err()
+    assert lib.nerfart_clip_vitb32_image_bwd_partial(one_, nb, 1, null, one_, one_, n1, 12, null) != 0 and "null g_feat" in err()
+    assert lib.nerfart_clip_vitb32_image_bwd_partial(one_, nb, 1, one_, null, one_, n1, 0, null) != 0 and "null g_feat" in err()
+    assert lib.nerfart_clip_vitb32_image_bwd(one_, nb, 1, one_, null, one_, n1, null) != 0 and "null g_feat" in err()
     assert lib.nerfart_resample_fwd(null, 2, 3, 8, 8, 0, 0, 8, 8, 4, 4, 1, null, null, null, null, 3, 4, 4, null) != 0 and "n_src" in err()
     assert lib.nerfart_resample_fwd(null, 1, 3, 8, 8, 0, 0, 8, 8, 4, 4, 7, null, null, null, null, 1, 4, 4, null) != 0 and "mode" in err()
     assert lib.nerfart_clip_style_heads(null, 17, null, null, null, null, 8, 79, 1.0, 0.2, 0.1, 2.0, 0.07, null, null, null) != 0 and "n_patches" in err()
