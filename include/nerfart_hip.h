@@ -532,6 +532,44 @@ int nerfart_mesh_compact_count(const int* label, const unsigned char* keep, cons
 int nerfart_mesh_compact_emit(const int* label, const unsigned char* keep, const int* faces, unsigned V, unsigned F, const void* ws, size_t ws_bytes,
                               int* src_vertex, int* faces_out, unsigned V_out, unsigned F_out, void* stream);
 
+/* ---- narrow-band SDF sweep (csrc/mesh_band.hip; mesh_util.banded_volume, extract_mesh(narrow_band=True)): the device side of a sweep that
+ * queries the SDF only in the bricks of the grid that can hold the isosurface.  Additions to ABI 5; no counterpart in the reference.  The SDF
+ * queries themselves are the caller's: these entry points make points, keep per-brick flags and move values.
+ *   THE GRID: points (i, j, k) in 0 .. N - 1, z fastest, vol [N, N, N] fp32.  Brick edge B in 2 .. 64; brick (bx, by, bz) owns the points with
+ *     i / B == bx, j / B == by, k / B == bz; nb = ceil(N / B) per axis (the last ragged when N % B != 0); n_bricks = nb^3; linear brick index
+ *     (bx nb + by) nb + bz.  A brick's probe is the grid point min(b B + B / 2, N - 1) per axis.  The coordinate of index i is
+ *     (float)((double)i * step + org) with the product and the sum rounded separately (NO fma): mesh_util.grid_points' bits.
+ *   nerfart_band_workspace_bytes: the size of nerfart_band_select's workspace (0 = bad dimensions, see nerfart_last_error).
+ *   nerfart_band_probe_points: pts [n_bricks, 3] = the probe points in brick order.
+ *   nerfart_band_select: which bricks become active now, as the ascending list of them.  NEWLY ACTIVE is, by mode: 0 = NOT (|probe[b] - level| >
+ *     threshold) in fp32 (a NaN probe is active), flag is overwritten;  1 = wanted[b] != 0 and flag[b] == 0;  2 = flag[b] == 0 (everything left).
+ *     Writes list [n] int32 (ascending brick indices), ptoff [n] uint32 (the number of owned points of the list's earlier bricks: where the
+ *     brick's points start in the evaluation order), counts [2] (DEVICE, 8-byte aligned) = {n, the owned points of the n bricks}; sets
+ *     flag[b] = 1 for them (flag, wanted: [n_bricks] uint8; list, ptoff: room for n_bricks) and clears wanted.  Scan and emit, no atomics.
+ *   nerfart_band_brick_points: the batch [first, first + count) of the evaluation order (bricks in list order, inside a brick x slowest / z
+ *     fastest over its OWNED points): pts [count, 3] and idx [count] uint32 = the linear grid index (i N + j) N + k.  n_list and n_points are
+ *     nerfart_band_select's counts.  A row that list / ptoff do not resolve gets idx = 0xffffffff.  count == 0 launches nothing.
+ *   nerfart_band_scatter: vol[idx[t]] = val[t] for t < count; an idx >= N^3 writes nothing.
+ *   nerfart_band_fill: every point of a brick with flag == 0 becomes probe[brick]; points of active bricks are not touched.  float4 stores when
+ *     N % 4 == 0, B % 4 == 0 and vol is 16-byte aligned.  A ragged last brick writes its owned points only.
+ *   nerfart_band_check: over all grid edges (per point toward +x, +y, +z where the neighbour exists), with marching cubes' predicate (inside iff
+ *     value < level; NaN is outside): an edge whose ends differ sets wanted[b] = 1 for every brick b with flag[b] == 0 that holds one of its ends
+ *     (plain byte stores).  Then counts [2] (DEVICE) = {bricks with wanted != 0, their owned points}: zeroed, summed per block, one integer
+ *     atomicAdd per block and counter - integer adds commute, two runs give the same numbers.  wanted must come in cleared
+ *     (nerfart_band_select leaves it so).
+ * Refused with 2 before any launch: a null pointer, N < 2, B outside 2 .. 64, N^3 >= 2^31, a mode outside 0 .. 2, counts not 8-byte aligned
+ * (select), a workspace smaller than the query's answer (or not 16-byte aligned), n_list == 0 or > n_bricks, n_points > N^3 or
+ * first + count > n_points (brick_points). */
+size_t nerfart_band_workspace_bytes(int N, int B);
+int nerfart_band_probe_points(int N, int B, double step, double org, float* pts, void* stream);
+int nerfart_band_select(int mode, const float* probe, float level, float threshold, int N, int B, unsigned char* flag, unsigned char* wanted,
+                        int* list, unsigned* ptoff, void* ws, size_t ws_bytes, unsigned* counts, void* stream);
+int nerfart_band_brick_points(const int* list, const unsigned* ptoff, unsigned n_list, unsigned n_points, unsigned first, unsigned count, int N, int B,
+                              double step, double org, float* pts, unsigned* idx, void* stream);
+int nerfart_band_scatter(const float* val, const unsigned* idx, unsigned count, int N, float* vol, void* stream);
+int nerfart_band_fill(const float* probe, const unsigned char* flag, int N, int B, float* vol, void* stream);
+int nerfart_band_check(const float* vol, float level, const unsigned char* flag, int N, int B, unsigned char* wanted, unsigned* counts, void* stream);
+
 /* ---- VGG16 perceptual term (criteria/perp_loss.py:9-57): torchvision vgg16.features[:16] (through relu3_3) as
  * implicit-GEMM 3 x 3 convolutions on v_mfma_f32_32x32x2_f32 (fp32 operands as the reference's net; csrc/vgg_conv.hip), L1
  * between prediction and target features.

@@ -35,7 +35,7 @@ def csrc_sha256() -> str:
         h.update(open(f, "rb").read())
     return h.hexdigest()
 
-_p, _i, _f, _ll = C.c_void_p, C.c_int, C.c_float, C.c_longlong
+_p, _i, _f, _ll, _d = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_double
 _SIGS = {
     "nerfart_abi_version": (_i, []),
     "nerfart_last_error": (C.c_char_p, []),
@@ -145,6 +145,13 @@ _SIGS = {
     "nerfart_mesh_compact_workspace_bytes": (_ll, [_i, _i]),
     "nerfart_mesh_compact_count": (_i, [_p, _p, _p, _i, _i, _p, _ll, _p, _p]),
     "nerfart_mesh_compact_emit": (_i, [_p, _p, _p, _i, _i, _p, _ll, _p, _p, _i, _i, _p]),
+    "nerfart_band_workspace_bytes": (_ll, [_i, _i]),
+    "nerfart_band_probe_points": (_i, [_i, _i, _d, _d, _p, _p]),
+    "nerfart_band_select": (_i, [_i, _p, _f, _f, _i, _i, _p, _p, _p, _p, _p, _ll, _p, _p]),
+    "nerfart_band_brick_points": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _d, _d, _p, _p, _p]),
+    "nerfart_band_scatter": (_i, [_p, _p, _i, _i, _p, _p]),
+    "nerfart_band_fill": (_i, [_p, _p, _i, _i, _p, _p]),
+    "nerfart_band_check": (_i, [_p, _f, _p, _i, _i, _p, _p, _p]),
     "nerfart_pack_surface_blob": (_i, [_i, _i, _p, _p, _p, _p, _ll, _p, _ll, _p]),
     "nerfart_pack_radiance_blob": (_i, [_i, _i, _p, _p, _p, _p, _p, _p, _p, _ll, _p, _ll, _p]),
     "nerfart_pack_plan_debug": (_i, [_i, _i, _i] + [_p] * 6),
@@ -464,6 +471,94 @@ def mesh_compact(label, keep, faces, V: int):
     ws, counts = mesh_compact_count(label, keep, faces, V)
     V_out, F_out = (int(c) for c in counts.cpu())
     return mesh_compact_emit(label, keep, faces, V, ws, V_out, F_out)
+
+
+def band_bricks(N: int, B: int) -> int:
+    """Bricks of edge B in an N^3 grid: ceil(N / B)^3 (csrc/mesh_band.hip)."""
+    return (-(-int(N) // int(B))) ** 3
+
+
+def band_workspace_bytes(N: int, B: int) -> int:
+    """nerfart_band_workspace_bytes; bad dimensions (N < 2, B outside 2 .. 64, N^3 >= 2^31) raise with the library's message."""
+    n = int(lib.nerfart_band_workspace_bytes(int(N), int(B)))
+    _check(0 if n else 2, "nerfart_band_workspace_bytes")
+    return n
+
+
+def band_probe_points(N: int, B: int, step: float, org: float, device):
+    """nerfart_band_probe_points: pts [ceil(N / B)^3, 3] float32 - the probe grid point of every brick, in mesh_util.grid_points' bits."""
+    band_workspace_bytes(N, B)                                         # the dimensions, refused before anything is allocated
+    pts = torch.empty(band_bricks(N, B), 3, dtype=torch.float32, device=device)
+    _check(lib.nerfart_band_probe_points(int(N), int(B), float(step), float(org), _dev(pts, name="pts"), _stream()), "nerfart_band_probe_points")
+    return pts
+
+
+class BandState:
+    """The per-brick arrays of one banded sweep, all on `device`: flag / wanted [bricks] uint8, list [bricks] int32, ptoff [bricks] int32 (holding
+    uint32), the selection's workspace."""
+    def __init__(self, N: int, B: int, device):
+        self.N, self.B, self.bricks = int(N), int(B), band_bricks(N, B)
+        self.ws = torch.empty(band_workspace_bytes(N, B), dtype=torch.uint8, device=device)
+        self.flag = torch.zeros(self.bricks, dtype=torch.uint8, device=device)
+        self.wanted = torch.zeros(self.bricks, dtype=torch.uint8, device=device)
+        self.list = torch.empty(self.bricks, dtype=torch.int32, device=device)
+        self.ptoff = torch.empty(self.bricks, dtype=torch.int32, device=device)
+
+
+def band_select(state: BandState, mode: int, probe=None, level: float = 0.0, threshold: float = 0.0):
+    """nerfart_band_select on state: the int32 device tensor counts [2] = (newly active bricks, their owned points); state.list / state.ptoff hold
+    the ascending list, state.flag is updated, state.wanted cleared.  mode 0: the probe test on probe [bricks] (fp32); 1: the wanted bricks;
+    2: every brick not yet active.  No host synchronisation."""
+    if probe is not None and probe.shape != (state.bricks,):
+        raise NerfartHipError(f"probe must be [{state.bricks}] (got {tuple(probe.shape)})")
+    counts = torch.empty(2, dtype=torch.int32, device=state.flag.device)
+    _check(lib.nerfart_band_select(int(mode), _dev(probe, name="probe"), float(level), float(threshold), state.N, state.B, state.flag.data_ptr(),
+                                   state.wanted.data_ptr(), state.list.data_ptr(), state.ptoff.data_ptr(), state.ws.data_ptr(), state.ws.numel(),
+                                   counts.data_ptr(), _stream()), "nerfart_band_select")
+    return counts
+
+
+def band_brick_points(state: BandState, n_list: int, n_points: int, first: int, count: int, step: float, org: float):
+    """nerfart_band_brick_points: (pts [count, 3] float32, idx [count] int32 - the linear grid indices) of the points first .. first + count of
+    the evaluation order of band_select's list (n_list bricks, n_points points)."""
+    dev = state.flag.device
+    pts = torch.empty(int(count), 3, dtype=torch.float32, device=dev)
+    idx = torch.empty(int(count), dtype=torch.int32, device=dev)
+    _check(lib.nerfart_band_brick_points(state.list.data_ptr(), state.ptoff.data_ptr(), int(n_list), int(n_points), int(first), int(count), state.N,
+                                         state.B, float(step), float(org), pts.data_ptr(), idx.data_ptr(), _stream()), "nerfart_band_brick_points")
+    return pts, idx
+
+
+def _band_volume(vol, N: int):
+    if tuple(vol.shape) != (N, N, N):
+        raise NerfartHipError(f"the volume must be [{N}, {N}, {N}] (got {tuple(vol.shape)})")
+    return _dev(vol, name="vol")
+
+
+def band_scatter(val, idx, vol):
+    """nerfart_band_scatter: vol.view(-1)[idx] = val (val [M] float32, idx [M] int32 from band_brick_points), in place."""
+    M = idx.shape[0]
+    if val.shape != (M,):
+        raise NerfartHipError(f"val must be [{M}] (got {tuple(val.shape)})")
+    _check(lib.nerfart_band_scatter(_dev(val, name="val"), _dev(idx, torch.int32, "idx"), M, int(vol.shape[0]), _band_volume(vol, int(vol.shape[0])),
+                                    _stream()), "nerfart_band_scatter")
+
+
+def band_fill(state: BandState, probe, vol):
+    """nerfart_band_fill: every point of a brick that is not active gets probe [bricks] of its brick, in place on vol [N, N, N]."""
+    if probe.shape != (state.bricks,):
+        raise NerfartHipError(f"probe must be [{state.bricks}] (got {tuple(probe.shape)})")
+    _check(lib.nerfart_band_fill(_dev(probe, name="probe"), state.flag.data_ptr(), state.N, state.B, _band_volume(vol, state.N), _stream()),
+           "nerfart_band_fill")
+
+
+def band_check(state: BandState, vol, level: float):
+    """nerfart_band_check: marks in state.wanted the inactive bricks that hold an end of a sign-changing edge of vol; the int32 device tensor
+    counts [2] = (wanted bricks, their owned points).  No host synchronisation."""
+    counts = torch.empty(2, dtype=torch.int32, device=vol.device)
+    _check(lib.nerfart_band_check(_band_volume(vol, state.N), float(level), state.flag.data_ptr(), state.N, state.B, state.wanted.data_ptr(),
+                                  counts.data_ptr(), _stream()), "nerfart_band_check")
+    return counts
 
 
 def nabla_workspace(precision: int, device):

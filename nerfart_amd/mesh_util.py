@@ -20,6 +20,8 @@ against the SDF without leaving the edge (`refine_vertices`; csrc/mesh_vertices.
 colours (the radiance net looking down the normal; `vertex_attributes`) as extra PLY vertex properties.
 `extract_mesh(keep_largest=, min_component_faces=)` drops the floaters: `mesh_components` labels the connected components of the indexed mesh
 on the GPU (csrc/mesh_components.hip), `filter_components` keeps the largest ones and compacts vertices and faces.
+`extract_mesh(narrow_band=True)` replaces the N^3 sweep by `banded_volume`: the SDF is queried only in the bricks of the grid that can hold the
+level set, the rest is filled with a value of the right sign, and the result checks and repairs itself (csrc/mesh_band.hip).
 """
 import numpy as np
 import torch
@@ -39,10 +41,96 @@ def grid_points(N: int, volume_size: float, device, start: int = 0, stop: int = 
     return torch.stack([ix * step + org, iy * step + org, iz * step + org], dim=-1).float()
 
 
+BAND_LIPSCHITZ = 1.8          # default bound on |grad sdf| of the narrow-band sweep: how it was chosen is in DESIGN.md 4.7
+
+
+def band_threshold(N: int, volume_size: float, brick: int, lipschitz: float) -> float:
+    """The narrow-band test's threshold: lipschitz * reach with reach = sqrt(3) * max(B // 2 + 1, B - B // 2) * step - the largest distance from a
+    brick's probe to a point of the brick's box extended by one grid step on every side.  Computed in double, rounded to float32."""
+    reach_steps = max(brick // 2 + 1, brick - brick // 2)
+    return float(np.float32(float(lipschitz) * (np.sqrt(3.0) * reach_steps * (volume_size / (N - 1)))))
+
+
 @torch.no_grad()
-def sdf_volume(implicit_surface, volume_size: float = 2.0, N: int = 512, chunk: int = 1 << 24, reference_shear: bool = False):
-    """[N, N, N] float32 (on the GPU): sdf at the grid points (mesh_util.py:82-111)."""
+def banded_volume(query_fn, N: int, volume_size: float, level: float = 0.0, brick: int = 8, lipschitz: float = BAND_LIPSCHITZ,
+                  max_repair_rounds: int = 4, chunk: int = 1 << 24, device=None):
+    """The [N, N, N] float32 volume of sdf_volume's regular grid with query_fn (pts [M, 3] float32 on the GPU -> values [M] float32) spent only where
+    the level set can be (csrc/mesh_band.hip): (vol, info).
+
+    The grid is cut into bricks of brick^3 points (the last of an axis ragged).  Each brick is queried once, at its probe point
+    min(b * brick + brick // 2, N - 1); it is ACTIVE iff NOT |f(probe) - level| > band_threshold(...) (float32; a NaN probe is active).  Every owned
+    point of every active brick is queried (bricks ascending, inside a brick z fastest, at most `chunk` points per call) and stored; every point of
+    an inactive brick gets its brick's probe value.  Then the volume is checked: an edge of the grid whose ends differ in `value < level` and that
+    has an end in an inactive brick makes that brick wanted; the wanted bricks are activated and queried and the check runs again, at most
+    max_repair_rounds times, after which every remaining brick is activated (the volume is then the dense one).  Host reads: one after the
+    probe test, one per check.
+
+    At exit no sign-changing edge has a filled end.  If every filled value also has the true sign - which holds whenever lipschitz bounds
+    |grad f| - the volume has the dense sweep's case index in every cell and its values at both ends of every crossing edge, so marching_cubes,
+    hip.mc_emit_edges and everything after them give the dense sweep's bits (query_fn must give a point the same value in any batch: K2 does).
+    The repair loop is a safety net for a bound that fails along a connected piece of surface, not a proof: a piece of surface that lies wholly
+    inside inactive bricks of one sign is NOT found.  A trained field may need a larger lipschitz than the default.
+
+    info: bricks (their number), active (newly active bricks: after the probe test, then per repair round, then of the dense completion if it
+    ran), evaluated_points (owned points queried, the `bricks` probe queries not counted), repair_rounds, completed_dense, threshold."""
+    from . import hip
+    N, B, chunk, max_repair_rounds = int(N), int(brick), int(chunk), int(max_repair_rounds)
+    if chunk < 1 or max_repair_rounds < 0:
+        raise ValueError(f"banded_volume: chunk must be >= 1 and max_repair_rounds >= 0 (got {chunk}, {max_repair_rounds})")
+    if not (float(lipschitz) > 0.0 and np.isfinite(lipschitz)):
+        raise ValueError(f"banded_volume: lipschitz must be positive and finite (got {lipschitz})")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    state = hip.BandState(N, B, dev)                                 # refuses N < 2, brick outside 2 .. 64, N^3 >= 2^31
+    step, org = volume_size / (N - 1), -volume_size / 2.0           # grid_points' expressions
+    thr = band_threshold(N, volume_size, B, lipschitz)
+    query = lambda pts: query_fn(pts).reshape(-1)
+    ppts = hip.band_probe_points(N, B, step, org, dev)
+    probe = torch.cat([query(ppts[s:s + chunk]) for s in range(0, state.bricks, chunk)]).contiguous()
+    vol = torch.empty(N, N, N, dtype=torch.float32, device=dev)
+    info = {"bricks": state.bricks, "active": [], "evaluated_points": 0, "repair_rounds": 0, "completed_dense": False, "threshold": thr}
+
+    def evaluate(n_list, n_points):
+        info["active"].append(n_list)
+        info["evaluated_points"] += n_points
+        for s in range(0, n_points, chunk):
+            pts, idx = hip.band_brick_points(state, n_list, n_points, s, min(chunk, n_points - s), step, org)
+            hip.band_scatter(query(pts), idx, vol)
+
+    n_list, n_points = (int(c) for c in hip.band_select(state, 0, probe, level, thr).cpu())
+    hip.band_fill(state, probe, vol)
+    evaluate(n_list, n_points)
+    while True:
+        n_list, n_points = (int(c) for c in hip.band_check(state, vol, level).cpu())
+        if n_list == 0:
+            break
+        if info["repair_rounds"] < max_repair_rounds:
+            hip.band_select(state, 1)
+            info["repair_rounds"] += 1
+            evaluate(n_list, n_points)
+        else:
+            hip.band_select(state, 2)
+            info["completed_dense"] = True
+            evaluate(state.bricks - sum(info["active"]), N ** 3 - info["evaluated_points"])
+            break
+    return vol, info
+
+
+@torch.no_grad()
+def sdf_volume(implicit_surface, volume_size: float = 2.0, N: int = 512, chunk: int = 1 << 24, reference_shear: bool = False,
+               narrow_band: bool = False, band_brick: int = 8, band_lipschitz: float = BAND_LIPSCHITZ, level: float = 0.0, band_info: dict = None):
+    """[N, N, N] float32 (on the GPU): sdf at the grid points (mesh_util.py:82-111).  narrow_band=True (regular grid only): banded_volume with
+    implicit_surface.forward around `level` - true values wherever marching cubes reads them, probe values of the right sign elsewhere; a dict
+    passed as band_info receives banded_volume's info.  narrow_band=False: the dense sweep, untouched."""
     dev = next(implicit_surface.parameters()).device
+    if narrow_band:
+        if reference_shear:
+            raise ValueError("sdf_volume: narrow_band needs the regular grid (the bound of the band test is stated on its lattice, not on the "
+                             "sheared one)")
+        vol, info = banded_volume(implicit_surface.forward, N, volume_size, level=level, brick=band_brick, lipschitz=band_lipschitz, chunk=chunk,
+                                  device=dev)
+        if band_info is not None:
+            band_info.update(info)
+        return vol
     out = torch.empty(N ** 3, dtype=torch.float32, device=dev)
     for s in range(0, N ** 3, chunk):
         e = min(s + chunk, N ** 3)
@@ -194,14 +282,16 @@ def write_ply(path, verts, faces, normals=None, colors=None):
 
 @torch.no_grad()
 def _extract_mesh_with_vertex_data(implicit_surface, volume_size, level, N, filepath, chunk, refine_evals, vertex_normals, color_model,
-                                   keep_largest=None, min_component_faces=None):
+                                   keep_largest=None, min_component_faces=None, narrow_band=False, band_brick=8, band_lipschitz=BAND_LIPSCHITZ,
+                                   band_info=None):
     """extract_mesh with any of refine_evals / vertex_normals / color_model set: every vertex is (edge, t); positions are written in the placement
     frame, every network query is made in the model's frame, so the refinement does not depend on how the mesh is placed.  Components are
     dropped once, at the end, from positions, faces, normals and colours together."""
     from . import hip
     if refine_evals < 0:
         raise ValueError(f"extract_mesh: refine_evals must be >= 0 (got {refine_evals})")
-    vol = sdf_volume(implicit_surface, volume_size, N, chunk)
+    vol = (sdf_volume(implicit_surface, volume_size, N, chunk, narrow_band=True, band_brick=band_brick, band_lipschitz=band_lipschitz, level=level,
+                      band_info=band_info) if narrow_band else sdf_volume(implicit_surface, volume_size, N, chunk))
     ws, counts = hip.mc_count(vol, level)
     V, F, bad = (int(c) for c in counts.cpu())
     if bad:
@@ -228,7 +318,8 @@ def _extract_mesh_with_vertex_data(implicit_surface, volume_size, level, N, file
 
 def extract_mesh(implicit_surface, volume_size=2.0, level=0.0, N=512, filepath="./surface.ply", show_progress=True, chunk=1 << 24,
                  reference_shear: bool = False, backend: str = "native", refine_evals: int = 0, vertex_normals: bool = False, color_model=None,
-                 keep_largest: int = None, min_component_faces: int = None):
+                 keep_largest: int = None, min_component_faces: int = None, narrow_band: bool = False, band_brick: int = 8,
+                 band_lipschitz: float = BAND_LIPSCHITZ, band_info: dict = None):
     """mesh_util.extract_mesh: SDF volume -> marching cubes -> .ply.  backend="native" (default): marching_cubes + write_ply above, nothing
     third-party, the volume stays on the GPU; backend="skimage": the reference's route (needs scikit-image and plyfile).  Both place the mesh as
     the reference does: spacing volume_size / N, offset -volume_size / 2 (mesh_util.py:112).  reference_shear=True samples
@@ -243,7 +334,19 @@ def extract_mesh(implicit_surface, volume_size=2.0, level=0.0, N=512, filepath="
 
     keep_largest / min_component_faces (native backend, the sheared grid included; both None: the paths above, untouched) drop the floaters
     before the file is written: only the keep_largest largest connected components, and / or only those of at least min_component_faces faces,
-    survive (filter_components; csrc/mesh_components.hip), with their vertices, normals and colours."""
+    survive (filter_components; csrc/mesh_components.hip), with their vertices, normals and colours.
+
+    narrow_band=True (native backend, regular grid; False: the paths above, untouched) sweeps the SDF only in the bricks of band_brick^3 grid
+    points that can hold the level set, given |grad sdf| <= band_lipschitz (banded_volume; csrc/mesh_band.hip): the file is the dense sweep's byte
+    for byte when the bound holds.  A piece of surface lying wholly inside bricks the bound wrongly ruled out is not found; a dict passed as
+    band_info receives the sweep's counts.  ValueError with reference_shear=True (not the lattice the bound is stated on) and with
+    backend="skimage" (Lewiner's ambiguity tests read corner values that would be fill values)."""
+    if narrow_band and reference_shear:
+        raise ValueError("extract_mesh: narrow_band needs the regular grid (reference_shear=True samples a sheared lattice, on which the bound of "
+                         "the band test is not stated)")
+    if narrow_band and backend == "skimage":
+        raise ValueError("extract_mesh: narrow_band needs backend='native' (scikit-image's Lewiner variant reads corner values that would be fill "
+                         "values)")
     filtering = keep_largest is not None or min_component_faces is not None
     if filtering and backend != "native":
         raise ValueError("extract_mesh: keep_largest / min_component_faces need backend='native' (the components are found on the GPU)")
@@ -252,9 +355,11 @@ def extract_mesh(implicit_surface, volume_size=2.0, level=0.0, N=512, filepath="
             raise ValueError("extract_mesh: refine_evals / vertex_normals / color_model need backend='native' and the regular grid "
                              "(the sheared grid has no regular frame, scikit-image gives no edge table)")
         return _extract_mesh_with_vertex_data(implicit_surface, volume_size, level, N, filepath, chunk, int(refine_evals), vertex_normals, color_model,
-                                              keep_largest, min_component_faces)
+                                              keep_largest, min_component_faces, narrow_band, band_brick, band_lipschitz, band_info)
     if backend == "native":
-        vol = sdf_volume(implicit_surface, volume_size, N, chunk, reference_shear=reference_shear)
+        vol = (sdf_volume(implicit_surface, volume_size, N, chunk, narrow_band=True, band_brick=band_brick, band_lipschitz=band_lipschitz,
+                          level=level, band_info=band_info) if narrow_band
+               else sdf_volume(implicit_surface, volume_size, N, chunk, reference_shear=reference_shear))
         verts, faces = marching_cubes(vol, level=level, spacing=[volume_size / N] * 3, origin=[-volume_size / 2.0] * 3)
         if filtering:
             verts, faces, _ = filter_components(verts, faces, keep_largest, min_component_faces)

@@ -2,7 +2,9 @@
 """Mesh extraction timing on one MI355X: the N^3 SDF sweep of the sphere-initialised VolSDF model (mesh_util.sdf_volume) beside the native
 marching cubes on the same grid (nerfart_mc_count = classify + scans, nerfart_mc_emit).  Warm, HIP events, median of --iters runs.  Prints one
 JSON line (NOT the driver's bench contract - that is bench.py).  Per-kernel times (classify apart from the scans) come from running this file
-under `rocprofv3 --kernel-trace --stats` with --no-sdf.  DESIGN.md 4.7 says which of these figures have been taken."""
+under `rocprofv3 --kernel-trace --stats` with --no-sdf.  `--narrow_band [--band_brick B]` adds, in the same job, the narrow-band sweep's median
+time (banded_volume_ms, beside the dense sdf_volume_ms), the share of grid points it queried, its repair rounds and whether marching cubes gives
+the dense sweep's mesh bit for bit.  DESIGN.md 4.7 says which of these figures have been taken."""
 import argparse, json, os, statistics, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,6 +29,8 @@ def main():
     ap.add_argument("--volume_size", type=float, default=3.0)
     ap.add_argument("--iters", type=int, default=12)
     ap.add_argument("--no-sdf", action="store_true", help="time the extractor only (the volume is still swept once)")
+    ap.add_argument("--narrow_band", action="store_true", help="also time the narrow-band sweep (mesh_util.banded_volume) and compare its mesh")
+    ap.add_argument("--band_brick", type=int, default=8)
     args = ap.parse_args()
     from nerfart_amd import scene, mesh_util, hip
     dev = torch.device("cuda", 0)
@@ -46,6 +50,19 @@ def main():
     res["mc_emit_ms"], _ = timed(lambda: hip.mc_emit(vol, 0.0, [-vs / 2] * 3, [vs / N] * 3, ws, V, F), args.iters)
     res.update(vertices=V, triangles=F, workspace_MiB=round(ws.numel() / 2 ** 20, 1),
                classify_bytes=N ** 3 * (4 + 2))                    # the volume read once + two bytes written per point
+    if args.narrow_band:                                           # the banded sweep beside the dense one above: same job, same model, same grid
+        info = {}
+        banded = lambda: mesh_util.sdf_volume(model.implicit_surface, volume_size=vs, N=N, narrow_band=True, band_brick=args.band_brick, band_info=info)
+        bvol = banded()                                            # warm-up
+        verts, faces = hip.mc_emit(vol, 0.0, [-vs / 2] * 3, [vs / N] * 3, ws, V, F)
+        res["mesh_equal"] = False                                  # stays False if the banded volume raises in marching_cubes
+        bverts, bfaces = mesh_util.marching_cubes(bvol, 0.0, spacing=[vs / N] * 3, origin=[-vs / 2] * 3)
+        res["mesh_equal"] = bool(torch.equal(verts.view(torch.int32), bverts.view(torch.int32)) and torch.equal(faces, bfaces))
+        del bvol, verts, faces, bverts, bfaces
+        res["banded_volume_ms"], _ = timed(banded, max(3, args.iters // 4))
+        res.update(band_brick=args.band_brick, band_lipschitz=mesh_util.BAND_LIPSCHITZ, evaluated_share=round(info["evaluated_points"] / N ** 3, 5),
+                   probe_share=round(info["bricks"] / N ** 3, 5), repair_rounds=info["repair_rounds"], completed_dense=info["completed_dense"],
+                   active_bricks=info["active"], bricks=info["bricks"])
     print(json.dumps(res))
 
 

@@ -6,7 +6,9 @@ the GPU (nerfart_amd.mesh_util.extract_mesh: the SDF kernel, csrc/marching_cubes
 
 `--refine 5 --normals --colors` (no reference counterpart) moves the vertices onto the surface along their grid edges and adds per-vertex normals and
 colours to the file; without them the file is the reference's two elements.  `--keep_largest 1` (or `--min_faces M`) drops the floaters: only the
-largest connected components of the surface are written.  Without --load_pt the mesh is the model's sphere initialisation.  `--k1:k2 v` overrides of the config work as everywhere (nerfart_amd.config)."""
+largest connected components of the surface are written.  `--narrow_band [--band_brick B --band_lipschitz L]` sweeps the SDF only near the surface
+(mesh_util.banded_volume; the same file when L bounds |grad sdf|) and prints the sweep's counts as one JSON line.  Without --load_pt the mesh is the model's sphere initialisation.  `--k1:k2 v` overrides of the config work as everywhere (nerfart_amd.config)."""
+import json
 import os
 import sys
 
@@ -19,6 +21,7 @@ sys.path.insert(0, ROOT)
 def parse(argv=None):
     """(args, config) from the command line: the reference's parser (--config / --resume_dir) plus this tool's options."""
     from nerfart_amd import config as cfg
+    from nerfart_amd.mesh_util import BAND_LIPSCHITZ
     parser = cfg.create_args_parser()
     parser.add_argument("--load_pt", type=str, default=None, help="checkpoint (torch.save({'model': state_dict, ...})); default: the initialisation")
     parser.add_argument("--N", type=int, default=512, help="grid points per axis")
@@ -33,6 +36,11 @@ def parse(argv=None):
     parser.add_argument("--keep_largest", type=int, default=None, help="keep only the K largest connected components of the mesh (by faces): "
                                                                        "drops the floaters")
     parser.add_argument("--min_faces", type=int, default=None, help="keep only the connected components of at least M faces")
+    parser.add_argument("--narrow_band", action="store_true", help="query the SDF only in the bricks of the grid that can hold the surface (the same "
+                                                                   "file when --band_lipschitz bounds |grad sdf|); prints the sweep's counts")
+    parser.add_argument("--band_brick", type=int, default=8, help="grid points per brick edge of --narrow_band (2 .. 64)")
+    parser.add_argument("--band_lipschitz", type=float, default=BAND_LIPSCHITZ, help="the bound on |grad sdf| --narrow_band relies on; a trained "
+                                                                                     "checkpoint may need more than the default")
     args, unknown = parser.parse_known_args(argv)
     return args, cfg.load_config(args, unknown)
 
@@ -47,9 +55,13 @@ def main():
         state = torch.load(args.load_pt, map_location="cpu")
         model.load_state_dict(state["model"] if "model" in state else state)
     model.to(dev)
+    info = {}
     path = mesh_util.extract_mesh(model.implicit_surface, volume_size=args.volume_size, level=args.level, N=args.N, filepath=args.out, chunk=args.chunk,
                                   refine_evals=args.refine, vertex_normals=args.normals, color_model=model if args.colors else None,
-                                  keep_largest=args.keep_largest, min_component_faces=args.min_faces)
+                                  keep_largest=args.keep_largest, min_component_faces=args.min_faces, narrow_band=args.narrow_band,
+                                  band_brick=args.band_brick, band_lipschitz=args.band_lipschitz, band_info=info)
+    if args.narrow_band:
+        print(json.dumps(info))
     print(path)
 
 
