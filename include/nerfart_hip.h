@@ -532,6 +532,45 @@ int nerfart_mesh_compact_count(const int* label, const unsigned char* keep, cons
 int nerfart_mesh_compact_emit(const int* label, const unsigned char* keep, const int* faces, unsigned V, unsigned F, const void* ws, size_t ws_bytes,
                               int* src_vertex, int* faces_out, unsigned V_out, unsigned F_out, void* stream);
 
+/* ---- mesh simplification by vertex clustering with quadric error metrics (csrc/mesh_simplify.hip; mesh_util.simplify_clusters,
+ * extract_mesh(simplify_factor=); Lindstrom 2000, the representative placed as in dual contouring).  Additions to ABI 5; no counterpart in the
+ * reference.  verts [V, 3] fp32 in GRID coordinates - grid point (i, j, k) sits at (i, j, k), nerfart_mc_emit with spacing 1, origin 0 -,
+ * faces [F, 3] int32, the cluster factor c >= 2, the grid (nx, ny, nz).  tests/mesh_simplify_ref.py states all of this in numpy.
+ *   THE CLUSTER of a vertex: per axis min((int)floorf(x), n - 1) / c in INTEGER division - no floating-point division decides a cluster, so a
+ *     vertex exactly on a grid point lands in the same cluster in any implementation.  The lattice has l = ceil(n / c) cells per axis (the last
+ *     ragged when n % c != 0); the linear cell index is x-major like the volume: (kx ly + ky) lz + kz.  A vertex with a non-finite coordinate or
+ *     one outside [0, n - 1] is BAD: it joins nothing and sets the flag.
+ *   THE NUMBERING: the occupied cells in ascending linear order are the new vertices 0 .. V' - 1; cluster [V] int32 = the new vertex of every
+ *     old one (-1 for a bad one).
+ *   THE QUADRICS, per cluster in its local frame - origin at the cell's centre, unit = the cell's edge: p = (g - c (k + 1/2)) / c.  Every face
+ *     with (all indices in [0, V) and) n = (b - a) x (c - a) != 0 (edges in local units) adds the plane quadric (n . (x - a))^2, i.e.
+ *     A += n n^T and b += n (n . a), once to every DISTINCT cluster among its three vertices, `a` taken in that cluster's frame.  (The
+ *     constant a . A a does not enter the argmin and is not accumulated.)  Every cluster also sums its members' local positions and counts them.
+ *     The sums are ORDER-INDEPENDENT: every fp32 term enters a 64-bit integer sum as round(term 2^40) by an integer atomicAdd.  The quantum is
+ *     2^-40; a term with NOT |term| <= 2^6, or more than 2^16 face contributions or member vertices in one cluster, sets the flag - within the
+ *     guards every sum stays below 2^62 and cannot wrap.  Two runs give the same bits.
+ *   THE REPRESENTATIVE (fp64, one thread per cluster): x* = argmin x^T A x - 2 b^T x + lambda |x - m|^2 with m the mean member position and
+ *     lambda = reg tr(A) / 3 - so cond(A + lambda I) <= 1 + 3 / reg and no rank decision is made; tr(A) == 0 gives x* = m.  x* is clamped
+ *     component-wise to the cell [-1/2, 1/2]^3 and mapped back: verts_out [V', 3] fp32 = c (k + 1/2) + c x*, in grid coordinates.
+ *   THE FACES: every index goes through `cluster`; the triple is rotated so that its smallest index comes first (the orientation is kept);
+ *     a face with fewer than three distinct indices is dropped; of faces with the same rotated triple only the FIRST in input order survives;
+ *     the survivors are compacted in input order (csrc/pair_scan.h, no atomics): faces_out [F', 3] int32.  The duplicates are found with an
+ *     open-addressing table of face indices (atomicCAS from empty, atomicMin among equal keys) whose outcome - the smallest index per key -
+ *     does not depend on the order of work.
+ *   nerfart_mesh_simplify_workspace_bytes: the size of the caller's workspace for the two calls below (0 = refused, see nerfart_last_error).
+ *   nerfart_mesh_simplify_count: fills the workspace, cluster [V] and counts [3] (DEVICE, 8-byte aligned) = {V', F', 1 if anything was bad: a face
+ *     index outside [0, V), a bad vertex, a guard of the sums}.  Asynchronous.  With the flag set the other outputs mean nothing.
+ *   nerfart_mesh_simplify_emit: from the SAME, untouched workspace and cluster array: verts_out [V_out, 3] and faces_out [F_out, 3]; V_out and
+ *     F_out are the sizes of the caller's arrays (every write is checked against them); both 0 launches nothing.
+ * Refused with 2 before any launch: a null pointer (of an array that is not empty), c < 2, a grid dimension outside 1 .. 2^24, a lattice of 2^31
+ * cells or more, V >= 2^31, F >= 2^30, counts not 8-byte aligned, reg outside (0, 1e6], V_out > min(V, cells) or F_out > F, a workspace smaller
+ * than the query's answer (or not 16-byte aligned). */
+size_t nerfart_mesh_simplify_workspace_bytes(unsigned V, unsigned F, int c, int nx, int ny, int nz);
+int nerfart_mesh_simplify_count(const float* verts, const int* faces, unsigned V, unsigned F, int c, int nx, int ny, int nz, void* ws, size_t ws_bytes,
+                                int* cluster, unsigned* counts, void* stream);
+int nerfart_mesh_simplify_emit(const int* faces, unsigned V, unsigned F, int c, int nx, int ny, int nz, double reg, const void* ws, size_t ws_bytes,
+                               const int* cluster, float* verts_out, int* faces_out, unsigned V_out, unsigned F_out, void* stream);
+
 /* ---- narrow-band SDF sweep (csrc/mesh_band.hip; mesh_util.banded_volume, extract_mesh(narrow_band=True)): the device side of a sweep that
  * queries the SDF only in the bricks of the grid that can hold the isosurface.  Additions to ABI 5; no counterpart in the reference.  The SDF
  * queries themselves are the caller's: these entry points make points, keep per-brick flags and move values.

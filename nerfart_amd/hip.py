@@ -145,6 +145,9 @@ _SIGS = {
     "nerfart_mesh_compact_workspace_bytes": (_ll, [_i, _i]),
     "nerfart_mesh_compact_count": (_i, [_p, _p, _p, _i, _i, _p, _ll, _p, _p]),
     "nerfart_mesh_compact_emit": (_i, [_p, _p, _p, _i, _i, _p, _ll, _p, _p, _i, _i, _p]),
+    "nerfart_mesh_simplify_workspace_bytes": (_ll, [_i, _i, _i, _i, _i, _i]),
+    "nerfart_mesh_simplify_count": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _ll, _p, _p, _p]),
+    "nerfart_mesh_simplify_emit": (_i, [_p, _i, _i, _i, _i, _i, _i, _d, _p, _ll, _p, _p, _p, _i, _i, _p]),
     "nerfart_band_workspace_bytes": (_ll, [_i, _i]),
     "nerfart_band_probe_points": (_i, [_i, _i, _d, _d, _p, _p]),
     "nerfart_band_select": (_i, [_i, _p, _f, _f, _i, _i, _p, _p, _p, _p, _p, _ll, _p, _p]),
@@ -471,6 +474,50 @@ def mesh_compact(label, keep, faces, V: int):
     ws, counts = mesh_compact_count(label, keep, faces, V)
     V_out, F_out = (int(c) for c in counts.cpu())
     return mesh_compact_emit(label, keep, faces, V, ws, V_out, F_out)
+
+
+def _mesh_simplify_args(verts, faces, dims, factor):
+    V = int(verts.shape[0])
+    if verts.dim() != 2 or verts.shape[1] != 3:
+        raise NerfartHipError(f"verts must be [V, 3] (got {tuple(verts.shape)})")
+    fp, F = _mesh_faces(faces, V)
+    if len(dims) != 3:
+        raise NerfartHipError(f"the grid shape must be (nx, ny, nz) (got {tuple(dims)})")
+    return _dev(verts, name="verts"), fp, V, F, [int(factor)] + [int(d) for d in dims]
+
+
+def mesh_simplify_workspace_bytes(V: int, F: int, factor: int, dims) -> int:
+    """nerfart_mesh_simplify_workspace_bytes; a refusal (factor < 2, a lattice of 2^31 cells, V >= 2^31, F >= 2^30) raises with the library's message."""
+    n = int(lib.nerfart_mesh_simplify_workspace_bytes(int(V), int(F), int(factor), *[int(d) for d in dims]))
+    _check(0 if n else 2, "nerfart_mesh_simplify_workspace_bytes")
+    return n
+
+
+def mesh_simplify_count(verts, faces, dims, factor: int, ws=None):
+    """nerfart_mesh_simplify_count on verts [V, 3] (grid coordinates of a grid of dims = (nx, ny, nz)) and faces [F, 3] int32: (ws, cluster, counts)
+    - the filled workspace (uint8; a caller's own, or a fresh one: it must stay untouched until mesh_simplify_emit has run), cluster [V] int32 =
+    the new vertex of every old one, and the int32 device tensor counts [3] = (V', F', bad flag).  No host synchronisation."""
+    vp, fp, V, F, grid = _mesh_simplify_args(verts, faces, dims, factor)
+    if ws is None:
+        ws = torch.empty(mesh_simplify_workspace_bytes(V, F, factor, dims), dtype=torch.uint8, device=verts.device)
+    cluster = torch.empty(V, dtype=torch.int32, device=verts.device)
+    counts = torch.empty(3, dtype=torch.int32, device=verts.device)
+    _check(lib.nerfart_mesh_simplify_count(vp, fp, V, F, *grid, _dev(ws, torch.uint8, "ws"), ws.numel(), cluster.data_ptr(), counts.data_ptr(), _stream()),
+           "nerfart_mesh_simplify_count")
+    return ws, cluster, counts
+
+
+def mesh_simplify_emit(verts, faces, dims, factor: int, reg: float, ws, cluster, V_out: int, F_out: int):
+    """nerfart_mesh_simplify_emit: (verts' [V_out, 3] float32 in grid coordinates, faces' [F_out, 3] int32) from the workspace and the cluster array
+    mesh_simplify_count filled for the same mesh."""
+    _, fp, V, F, grid = _mesh_simplify_args(verts, faces, dims, factor)
+    if cluster.shape != (V,):
+        raise NerfartHipError(f"cluster must be [{V}] (got {tuple(cluster.shape)})")
+    out_v = torch.empty(int(V_out), 3, dtype=torch.float32, device=verts.device)
+    out_f = torch.empty(int(F_out), 3, dtype=torch.int32, device=verts.device)
+    _check(lib.nerfart_mesh_simplify_emit(fp, V, F, *grid, float(reg), _dev(ws, torch.uint8, "ws"), ws.numel(), _dev(cluster, torch.int32, "cluster"),
+                                          out_v.data_ptr(), out_f.data_ptr(), int(V_out), int(F_out), _stream()), "nerfart_mesh_simplify_emit")
+    return out_v, out_f
 
 
 def band_bricks(N: int, B: int) -> int:

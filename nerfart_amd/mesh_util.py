@@ -22,6 +22,8 @@ colours (the radiance net looking down the normal; `vertex_attributes`) as extra
 on the GPU (csrc/mesh_components.hip), `filter_components` keeps the largest ones and compacts vertices and faces.
 `extract_mesh(narrow_band=True)` replaces the N^3 sweep by `banded_volume`: the SDF is queried only in the bricks of the grid that can hold the
 level set, the rest is filled with a value of the right sign, and the result checks and repairs itself (csrc/mesh_band.hip).
+`extract_mesh(simplify_factor=c)` decimates the mesh before it is written: `simplify_clusters` merges the vertices of every block of c^3 grid
+cells into one, placed by the quadric error metric of the block's faces (csrc/mesh_simplify.hip).
 """
 import numpy as np
 import torch
@@ -157,6 +159,13 @@ def model_frame(N: int, volume_size: float):
     return [-volume_size / 2.0] * 3, [volume_size / (N - 1)] * 3
 
 
+def grid_to_frame(grid, origin, spacing):
+    """Grid coordinates [V, 3] (float32) in the frame (origin, spacing): origin + spacing * grid, one float32 product and one float32 sum per
+    coordinate - how extract_mesh(simplify_factor=) places the representatives simplify_clusters returns."""
+    o, s = (torch.tensor([float(x) for x in a], dtype=torch.float32, device=grid.device) for a in (origin, spacing))
+    return o + s * grid
+
+
 def placement_frame(N: int, volume_size: float):
     """(origin, spacing) the reference places its mesh with: spacing volume_size / N, offset -volume_size / 2 (mesh_util.py:112)."""
     return [-volume_size / 2.0] * 3, [volume_size / N] * 3
@@ -242,6 +251,31 @@ def filter_components(verts, faces, keep_largest=None, min_faces=None):
     return verts[src_vertex.long()], faces_out, src_vertex
 
 
+def simplify_clusters(verts_grid, faces, shape, factor, reg: float = 0.01):
+    """Vertex clustering with quadric error metrics (csrc/mesh_simplify.hip; the rules are in include/nerfart_hip.h): the vertices verts_grid [V, 3]
+    (float32, on the GPU, in GRID coordinates of a grid of shape = (nx, ny, nz): grid point (i, j, k) sits at (i, j, k)) are merged per block of
+    factor^3 grid cells; every occupied block becomes one vertex, placed at the minimum of its faces' plane quadrics, pulled toward the members'
+    mean by reg and kept inside the block.  Returns (verts' [V', 3] float32 in grid coordinates, faces' [F', 3] int32 - renumbered, rotated to
+    smallest index first, degenerate and duplicate faces dropped, in input order -, cluster [V] int32 - the new vertex of every old one).
+    Everything stays on the GPU; one host read (V', F', the flag) between counting and emitting; two calls give identical tensors.  ValueError:
+    factor < 2, reg not positive, CPU tensors, and a mesh the kernels flag - a face index outside [0, V), a non-finite vertex or one outside the
+    grid, or a cluster whose sums would leave their guards (edges longer than a few blocks, more than 2^16 faces in one block)."""
+    from . import hip
+    if int(factor) != factor or int(factor) < 2:
+        raise ValueError(f"simplify_clusters: factor must be an integer >= 2 (got {factor})")
+    if not (float(reg) > 0.0 and np.isfinite(reg)):
+        raise ValueError(f"simplify_clusters: reg must be positive and finite (got {reg})")
+    if not (torch.is_tensor(verts_grid) and torch.is_tensor(faces) and verts_grid.is_cuda and faces.is_cuda):
+        raise ValueError("simplify_clusters: verts_grid and faces must be tensors on the GPU (there is no CPU path)")
+    ws, cluster, counts = hip.mesh_simplify_count(verts_grid, faces, shape, int(factor))
+    V_out, F_out, bad = (int(c) for c in counts.cpu())
+    if bad:
+        raise ValueError(f"simplify_clusters: the mesh cannot be clustered - a face index outside [0, {int(verts_grid.shape[0])}), a vertex that is not "
+                         f"finite or not inside the grid {tuple(int(d) for d in shape)}, or a cluster whose sums would leave their guards")
+    out_v, out_f = hip.mesh_simplify_emit(verts_grid, faces, shape, int(factor), float(reg), ws, cluster, V_out, F_out)
+    return out_v, out_f, cluster
+
+
 def write_ply(path, verts, faces, normals=None, colors=None):
     """Binary little-endian PLY: `element vertex` with float x, y, z and `element face` with `property list uchar int vertex_indices` - the file
     plyfile writes for the reference's two elements (mesh_util.py:57-80).  verts [V, 3], faces [F, 3]: tensors or arrays.  Optional per-vertex
@@ -283,10 +317,12 @@ def write_ply(path, verts, faces, normals=None, colors=None):
 @torch.no_grad()
 def _extract_mesh_with_vertex_data(implicit_surface, volume_size, level, N, filepath, chunk, refine_evals, vertex_normals, color_model,
                                    keep_largest=None, min_component_faces=None, narrow_band=False, band_brick=8, band_lipschitz=BAND_LIPSCHITZ,
-                                   band_info=None):
-    """extract_mesh with any of refine_evals / vertex_normals / color_model set: every vertex is (edge, t); positions are written in the placement
-    frame, every network query is made in the model's frame, so the refinement does not depend on how the mesh is placed.  Components are
-    dropped once, at the end, from positions, faces, normals and colours together."""
+                                   band_info=None, simplify_factor=None, simplify_reg=0.01):
+    """extract_mesh with any of refine_evals / vertex_normals / color_model / simplify_factor set: every vertex is (edge, t); positions are written
+    in the placement frame, every network query is made in the model's frame, so the refinement does not depend on how the mesh is placed.
+    Without simplify_factor components are dropped once, at the end, from positions, faces, normals and colours together.  With it the
+    (refined) vertices are taken in grid coordinates, floaters go first - before clustering can weld them to the surface -, simplify_clusters
+    merges the rest, and normals and colours are queried at the NEW vertices only."""
     from . import hip
     if refine_evals < 0:
         raise ValueError(f"extract_mesh: refine_evals must be >= 0 (got {refine_evals})")
@@ -304,6 +340,19 @@ def _extract_mesh_with_vertex_data(implicit_surface, volume_size, level, N, file
     else:
         edge, _, t, _, _ = hip.mc_emit_edges(vol, level, ws, V)
     normals = colors = None
+    if simplify_factor is not None:
+        grid = hip.mesh_edge_points(edge, t, vol.shape, [0.0] * 3, [1.0] * 3)
+        if keep_largest is not None or min_component_faces is not None:
+            grid, faces, _ = filter_components(grid, faces, keep_largest, min_component_faces)
+        grid, faces, _ = simplify_clusters(grid, faces, vol.shape, simplify_factor, simplify_reg)
+        verts = grid_to_frame(grid, place_o, place_s)
+        if vertex_normals or color_model is not None:
+            pts = grid_to_frame(grid, *model_frame(N, volume_size))
+            if color_model is not None:
+                normals, colors = vertex_attributes(color_model, pts)
+            else:
+                normals = hip.normalize_dirs(implicit_surface.forward_with_nablas(pts)[1].contiguous()) if pts.shape[0] else pts
+        return write_ply(filepath, verts, faces, normals if vertex_normals else None, colors)
     if vertex_normals or color_model is not None:
         pts = hip.mesh_edge_points(edge, t, vol.shape, *model_frame(N, volume_size))
         if color_model is not None:
@@ -319,7 +368,7 @@ def _extract_mesh_with_vertex_data(implicit_surface, volume_size, level, N, file
 def extract_mesh(implicit_surface, volume_size=2.0, level=0.0, N=512, filepath="./surface.ply", show_progress=True, chunk=1 << 24,
                  reference_shear: bool = False, backend: str = "native", refine_evals: int = 0, vertex_normals: bool = False, color_model=None,
                  keep_largest: int = None, min_component_faces: int = None, narrow_band: bool = False, band_brick: int = 8,
-                 band_lipschitz: float = BAND_LIPSCHITZ, band_info: dict = None):
+                 band_lipschitz: float = BAND_LIPSCHITZ, band_info: dict = None, simplify_factor: int = None, simplify_reg: float = 0.01):
     """mesh_util.extract_mesh: SDF volume -> marching cubes -> .ply.  backend="native" (default): marching_cubes + write_ply above, nothing
     third-party, the volume stays on the GPU; backend="skimage": the reference's route (needs scikit-image and plyfile).  Both place the mesh as
     the reference does: spacing volume_size / N, offset -volume_size / 2 (mesh_util.py:112).  reference_shear=True samples
@@ -340,7 +389,18 @@ def extract_mesh(implicit_surface, volume_size=2.0, level=0.0, N=512, filepath="
     points that can hold the level set, given |grad sdf| <= band_lipschitz (banded_volume; csrc/mesh_band.hip): the file is the dense sweep's byte
     for byte when the bound holds.  A piece of surface lying wholly inside bricks the bound wrongly ruled out is not found; a dict passed as
     band_info receives the sweep's counts.  ValueError with reference_shear=True (not the lattice the bound is stated on) and with
-    backend="skimage" (Lewiner's ambiguity tests read corner values that would be fill values)."""
+    backend="skimage" (Lewiner's ambiguity tests read corner values that would be fill values).
+
+    simplify_factor=c >= 2 (native backend, regular grid; None: the paths above, untouched) merges the vertices of every block of c^3 grid cells
+    into one, placed by the quadrics of the block's faces (simplify_clusters; csrc/mesh_simplify.hip; simplify_reg pulls it toward the members'
+    mean): roughly c^2 times fewer triangles.  The order is marching cubes, refinement, keep_largest / min_component_faces, clustering, and only
+    then vertex_normals / color_model, queried at the new vertices.  ValueError with reference_shear=True (the clusters are blocks of the regular
+    lattice) and with backend="skimage" (the clustering runs on the GPU, on the native extractor's vertices)."""
+    if simplify_factor is not None and reference_shear:
+        raise ValueError("extract_mesh: simplify_factor needs the regular grid (reference_shear=True samples a sheared lattice, whose cells are not "
+                         "the blocks the clusters are made of)")
+    if simplify_factor is not None and backend == "skimage":
+        raise ValueError("extract_mesh: simplify_factor needs backend='native' (the clustering runs on the GPU, on the native extractor's vertices)")
     if narrow_band and reference_shear:
         raise ValueError("extract_mesh: narrow_band needs the regular grid (reference_shear=True samples a sheared lattice, on which the bound of "
                          "the band test is not stated)")
@@ -350,12 +410,13 @@ def extract_mesh(implicit_surface, volume_size=2.0, level=0.0, N=512, filepath="
     filtering = keep_largest is not None or min_component_faces is not None
     if filtering and backend != "native":
         raise ValueError("extract_mesh: keep_largest / min_component_faces need backend='native' (the components are found on the GPU)")
-    if refine_evals or vertex_normals or color_model is not None:
+    if refine_evals or vertex_normals or color_model is not None or simplify_factor is not None:
         if reference_shear or backend != "native":
             raise ValueError("extract_mesh: refine_evals / vertex_normals / color_model need backend='native' and the regular grid "
                              "(the sheared grid has no regular frame, scikit-image gives no edge table)")
         return _extract_mesh_with_vertex_data(implicit_surface, volume_size, level, N, filepath, chunk, int(refine_evals), vertex_normals, color_model,
-                                              keep_largest, min_component_faces, narrow_band, band_brick, band_lipschitz, band_info)
+                                              keep_largest, min_component_faces, narrow_band, band_brick, band_lipschitz, band_info,
+                                              simplify_factor, simplify_reg)
     if backend == "native":
         vol = (sdf_volume(implicit_surface, volume_size, N, chunk, narrow_band=True, band_brick=band_brick, band_lipschitz=band_lipschitz,
                           level=level, band_info=band_info) if narrow_band

@@ -4,7 +4,8 @@ marching cubes on the same grid (nerfart_mc_count = classify + scans, nerfart_mc
 JSON line (NOT the driver's bench contract - that is bench.py).  Per-kernel times (classify apart from the scans) come from running this file
 under `rocprofv3 --kernel-trace --stats` with --no-sdf.  `--narrow_band [--band_brick B]` adds, in the same job, the narrow-band sweep's median
 time (banded_volume_ms, beside the dense sdf_volume_ms), the share of grid points it queried, its repair rounds and whether marching cubes gives
-the dense sweep's mesh bit for bit.  DESIGN.md 4.7 says which of these figures have been taken."""
+the dense sweep's mesh bit for bit.  `--simplify C` adds the simplify stage on the same mesh: mesh_util.simplify_clusters' median time, its two
+halves (nerfart_mesh_simplify_count, _emit) and V, F -> V', F'.  DESIGN.md 4.7 says which of these figures have been taken."""
 import argparse, json, os, statistics, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -31,6 +32,7 @@ def main():
     ap.add_argument("--no-sdf", action="store_true", help="time the extractor only (the volume is still swept once)")
     ap.add_argument("--narrow_band", action="store_true", help="also time the narrow-band sweep (mesh_util.banded_volume) and compare its mesh")
     ap.add_argument("--band_brick", type=int, default=8)
+    ap.add_argument("--simplify", type=int, default=None, help="also time mesh_util.simplify_clusters with this cluster factor on the extracted mesh")
     args = ap.parse_args()
     from nerfart_amd import scene, mesh_util, hip
     dev = torch.device("cuda", 0)
@@ -63,6 +65,17 @@ def main():
         res.update(band_brick=args.band_brick, band_lipschitz=mesh_util.BAND_LIPSCHITZ, evaluated_share=round(info["evaluated_points"] / N ** 3, 5),
                    probe_share=round(info["bricks"] / N ** 3, 5), repair_rounds=info["repair_rounds"], completed_dense=info["completed_dense"],
                    active_bricks=info["active"], bricks=info["bricks"])
+    if args.simplify:                                              # the simplify stage on the mesh above, in grid coordinates
+        c = args.simplify
+        gverts, gfaces = hip.mc_emit(vol, 0.0, [0.0] * 3, [1.0] * 3, ws, V, F)
+        sws = torch.empty(hip.mesh_simplify_workspace_bytes(V, F, c, vol.shape), dtype=torch.uint8, device=dev)
+        out_v, out_f, cluster = mesh_util.simplify_clusters(gverts, gfaces, vol.shape, c)      # warm-up; the sizes
+        res["simplify_ms"], _ = timed(lambda: mesh_util.simplify_clusters(gverts, gfaces, vol.shape, c), args.iters)
+        res["simplify_count_ms"], _ = timed(lambda: hip.mesh_simplify_count(gverts, gfaces, vol.shape, c, ws=sws), args.iters)
+        res["simplify_emit_ms"], _ = timed(lambda: hip.mesh_simplify_emit(gverts, gfaces, vol.shape, c, 0.01, sws, cluster, out_v.shape[0], out_f.shape[0]),
+                                           args.iters)
+        res.update(simplify_factor=c, simplified_vertices=int(out_v.shape[0]), simplified_triangles=int(out_f.shape[0]),
+                   simplify_workspace_MiB=round(sws.numel() / 2 ** 20, 1))
     print(json.dumps(res))
 
 

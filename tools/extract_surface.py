@@ -7,7 +7,9 @@ the GPU (nerfart_amd.mesh_util.extract_mesh: the SDF kernel, csrc/marching_cubes
 `--refine 5 --normals --colors` (no reference counterpart) moves the vertices onto the surface along their grid edges and adds per-vertex normals and
 colours to the file; without them the file is the reference's two elements.  `--keep_largest 1` (or `--min_faces M`) drops the floaters: only the
 largest connected components of the surface are written.  `--narrow_band [--band_brick B --band_lipschitz L]` sweeps the SDF only near the surface
-(mesh_util.banded_volume; the same file when L bounds |grad sdf|) and prints the sweep's counts as one JSON line.  Without --load_pt the mesh is the model's sphere initialisation.  `--k1:k2 v` overrides of the config work as everywhere (nerfart_amd.config)."""
+(mesh_util.banded_volume; the same file when L bounds |grad sdf|) and prints the sweep's counts as one JSON line.  `--simplify C [--simplify_reg R]`
+decimates the mesh on the GPU before it is written: the vertices of every block of C^3 grid cells become one, placed by the quadric error metric of
+the block's faces (mesh_util.simplify_clusters), after the floaters are gone and before normals and colours are queried.  Without --load_pt the mesh is the model's sphere initialisation.  `--k1:k2 v` overrides of the config work as everywhere (nerfart_amd.config)."""
 import json
 import os
 import sys
@@ -41,6 +43,10 @@ def parse(argv=None):
     parser.add_argument("--band_brick", type=int, default=8, help="grid points per brick edge of --narrow_band (2 .. 64)")
     parser.add_argument("--band_lipschitz", type=float, default=BAND_LIPSCHITZ, help="the bound on |grad sdf| --narrow_band relies on; a trained "
                                                                                      "checkpoint may need more than the default")
+    parser.add_argument("--simplify", type=int, default=None, help="merge the vertices of every block of C^3 grid cells into one (C >= 2): roughly "
+                                                                   "C^2 times fewer triangles")
+    parser.add_argument("--simplify_reg", type=float, default=0.01, help="how strongly --simplify pulls a merged vertex toward the mean of its members "
+                                                                         "where the faces' planes do not fix it")
     args, unknown = parser.parse_known_args(argv)
     return args, cfg.load_config(args, unknown)
 
@@ -59,7 +65,8 @@ def main():
     path = mesh_util.extract_mesh(model.implicit_surface, volume_size=args.volume_size, level=args.level, N=args.N, filepath=args.out, chunk=args.chunk,
                                   refine_evals=args.refine, vertex_normals=args.normals, color_model=model if args.colors else None,
                                   keep_largest=args.keep_largest, min_component_faces=args.min_faces, narrow_band=args.narrow_band,
-                                  band_brick=args.band_brick, band_lipschitz=args.band_lipschitz, band_info=info)
+                                  band_brick=args.band_brick, band_lipschitz=args.band_lipschitz, band_info=info, simplify_factor=args.simplify,
+                                  simplify_reg=args.simplify_reg)
     if args.narrow_band:
         print(json.dumps(info))
     print(path)
