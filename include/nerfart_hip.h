@@ -113,7 +113,12 @@ int nerfart_radiance_fwd_rays(const float* rad_blob, int precision, int view_til
  * geometry-feature rows), g_n[M,3] (cotangent of the normal input), and bwd_dump (same layout: the deltas of
  * R0, R1, R2, R3 - each in the slot of the activation it multiplies - and the geometry-feature cotangent): the operands
  * of the weight-gradient reductions (dW_l = delta_l^T act_{l-1}: nerfart_wgrad_bf16 below; call sequence in nerfart_amd/autodiff.py).
- * At most 2^21 points per call. */
+ * Padded rows (M .. Mp-1; the reductions run over all Mp rows unmasked): a padded point is evaluated with every input 0 and
+ * d loss / d rgb = 0, so its activations (forward dump) are finite and its deltas and g_f (backward dump) are exactly 0 - every
+ * product row of a padded point is exactly 0.  A real point with d loss / d rgb = 0 has deltas, g_f, g_h7 and g_n exactly 0.  Both
+ * calls write every row of their dump and nothing past nerfart_radiance_dump_bytes(M); rgb_out, g_h7_out, g_n_out: rows 0..M-1 only.
+ * At most 2^21 points per call; every pointer argument must be non-NULL (refused by name before any launch).
+ * (tests/mlp_bwd_ref.py, tests/test_gpu_mlp_bwd.py) */
 long long nerfart_radiance_dump_bytes(long long M);
 int nerfart_radiance_fwd_dump(const float* rad_blob, int view_tiles, const float* pts, const float* view, long long M,
                               const float* nabla, const float* h7, float* rgb_out, void* dump, void* stream);
@@ -130,7 +135,13 @@ int nerfart_radiance_bwd(const float* rad_blob, long long M, const float* rgb, c
  * Both dumps are matrices [slot][2 Mp][256], Mp = M rounded up to 64: rows 0..Mp-1 of a slot hold the first, rows Mp..
  * the second quantity of the pair, per point; features in unit order; so dW_l is ONE GEMM over the stacked rows, read in
  * place.  (The softplus' slots 8..15 of f2_dump hold one value per point: rows 0..Mp-1 only, rows Mp.. are never written or read.)
- * At most 2^21 points per call.
+ * SDF layer 3 has 217 outputs: columns of features 217..255 of its slots (3, 11) are finite and meet zero weights; unit 7 (features
+ * 224..255) is written as zero bits.
+ * Padded rows (M .. Mp-1 of either half; the reductions run over all 2 Mp rows unmasked): a padded point is evaluated at pts = 0 with
+ * dir = 0 and zero cotangents, so its adot_l rows and its zbar_l rows are exactly 0 while their partners a_l and t_l d_l are finite
+ * - every product row of a padded point, zbar_l (x) a_{l-1} and (t_l d_l) (x) adot_{l-1}, is exactly 0.  The same holds for a real point:
+ * dir = 0 gives adot_l = 0, and dir = 0 with gbar_h7 = 0, gbar_sdf = 0 gives zbar_l = 0.  Neither call writes past its _dump_bytes(M).
+ * At most 2^21 points per call; every pointer argument must be non-NULL (refused by name before any launch).
  * The reductions are nerfart_wgrad_bf16 calls; the whole sequence - these two sweeps, the reductions, the un-permutation and the weight_norm chain
  * rule - is behind nerfart_sdf_param_bwd / nerfart_*_render_bwd + nerfart_fold_weight_grads / nerfart_weight_norm_bwd (csrc/render_backward.hip). */
 long long nerfart_sdf_fwd2_dump_bytes(long long M);

@@ -20,6 +20,8 @@
 //     point, the activation derivative is broadcast inside the quad with one DPP op.
 //   * persistent grid (one workgroup per CU), tiles grid-strided.
 #include "mlp_common.h"
+#include <initializer_list>
+#include <string>
 
 namespace nerfart {
 
@@ -755,13 +757,23 @@ int nerfart_radiance_fwd_rays(const float* blob, int precision, int view_tiles, 
 // ---- radiance net with activation dumps + its backward (row a19; split-bf16 blobs only) ----------------------
 long long nerfart_radiance_dump_bytes(long long M) { return (long long)radiance_dump_bytes(M); }
 
+// The per-sample backward entry points refuse every NULL pointer argument by name, and more than 2^21 points, before any launch.
+struct NamedArg { const char* name; const void* p; };
+static int check_dump_call(const char* who, long long M, std::initializer_list<NamedArg> args) {
+    if (M > (1ll << 21)) { set_last_error((std::string(who) + ": at most 2^21 points per call").c_str()); return 2; }
+    for (const NamedArg& a : args)
+        if (!a.p) { set_last_error((std::string(who) + ": " + a.name + " is NULL").c_str()); return 2; }
+    return 0;
+}
+
 int nerfart_radiance_fwd_dump(const float* rad_blob, int view_tiles, const float* pts, const float* view, long long M,
                               const float* nabla, const float* h7, float* rgb_out, void* dump, void* stream) {
     if (int rc = check_M(M)) return rc;
     if (M == 0) return 0;
+    if (int rc = check_dump_call("radiance_fwd_dump", M, {{"rad_blob", rad_blob}, {"pts", pts}, {"view", view}, {"nabla", nabla}, {"h7", h7},
+                                                          {"rgb_out", rgb_out}, {"dump", dump}})) return rc;
     PointSrc s = make_src(pts, view, nullptr, nullptr, nullptr, nullptr, 1, 0, M);
     if (int rc = validate_src(s)) return rc;
-    if (!dump) { set_last_error("radiance_fwd_dump: dump buffer is NULL"); return 2; }
     return radiance_fwd_dump_bf16(rad_blob, view_tiles, s, nabla, h7, rgb_out, dump, (hipStream_t)stream);
 }
 
@@ -769,7 +781,8 @@ int nerfart_radiance_bwd(const float* rad_blob, long long M, const float* rgb, c
                          float* g_h7_out, float* g_n_out, void* stream) {
     if (int rc = check_M(M)) return rc;
     if (M == 0) return 0;
-    if (!fwd_dump || !bwd_dump) { set_last_error("radiance_bwd: dump buffers are NULL"); return 2; }
+    if (int rc = check_dump_call("radiance_bwd", M, {{"rad_blob", rad_blob}, {"rgb", rgb}, {"g_rgb", g_rgb}, {"fwd_dump", fwd_dump}, {"bwd_dump", bwd_dump},
+                                                     {"g_h7_out", g_h7_out}, {"g_n_out", g_n_out}})) return rc;
     return radiance_bwd_bf16(rad_blob, M, rgb, g_rgb, fwd_dump, bwd_dump, g_h7_out, g_n_out, (hipStream_t)stream);
 }
 
@@ -780,7 +793,7 @@ long long nerfart_sdf_bwd2_dump_bytes(long long M) { return (long long)sdf_bwd2_
 int nerfart_sdf_fwd2(const float* surf_blob, const float* pts, const float* dir, long long M, void* f2_dump, void* stream) {
     if (int rc = check_M(M)) return rc;
     if (M == 0) return 0;
-    if (!pts || !dir || !f2_dump) { set_last_error("sdf_fwd2: NULL argument"); return 2; }
+    if (int rc = check_dump_call("sdf_fwd2", M, {{"surf_blob", surf_blob}, {"pts", pts}, {"dir", dir}, {"f2_dump", f2_dump}})) return rc;
     return sdf_fwd2_bf16(surf_blob, M, pts, dir, f2_dump, (hipStream_t)stream);
 }
 
@@ -788,7 +801,8 @@ int nerfart_sdf_bwd2(const float* surf_blob, long long M, const float* gbar_h7, 
                      void* stream) {
     if (int rc = check_M(M)) return rc;
     if (M == 0) return 0;
-    if (!gbar_h7 || !gbar_sdf || !f2_dump || !r2_dump) { set_last_error("sdf_bwd2: NULL argument"); return 2; }
+    if (int rc = check_dump_call("sdf_bwd2", M, {{"surf_blob", surf_blob}, {"gbar_h7", gbar_h7}, {"gbar_sdf", gbar_sdf}, {"f2_dump", f2_dump},
+                                                 {"r2_dump", r2_dump}})) return rc;
     return sdf_bwd2_bf16(surf_blob, M, gbar_h7, gbar_sdf, f2_dump, r2_dump, (hipStream_t)stream);
 }
 }  // extern "C"

@@ -317,3 +317,38 @@ def test_composite_entry_points_refuse_rows_without_an_interval():
         for P in (1, 0, 514, 1025):
             assert call(1, P) == 2 and "2 <= P <= 513" in err(), (P, err())
         assert call(0, 0) == 0
+
+
+def test_per_sample_backward_entry_points_refuse_null_pointers_without_a_gpu():
+    """nerfart_sdf_fwd2 / nerfart_sdf_bwd2 / nerfart_radiance_fwd_dump / nerfart_radiance_bwd refuse every NULL pointer argument, blob included, with a
+    message that names it, and more than 2^21 points, before any launch: non-null dummies that are never dereferenced, one NULL at a time."""
+    import ctypes as C
+    from nerfart_amd import hip
+    lib, null, one = hip.lib, None, C.c_void_p(16)
+
+    def err():
+        return lib.nerfart_last_error().decode()
+
+    M = 4
+    calls = {
+        "sdf_fwd2": (("surf_blob", "pts", "dir", "f2_dump"),
+                     lambda p, m: lib.nerfart_sdf_fwd2(p["surf_blob"], p["pts"], p["dir"], m, p["f2_dump"], null)),
+        "sdf_bwd2": (("surf_blob", "gbar_h7", "gbar_sdf", "f2_dump", "r2_dump"),
+                     lambda p, m: lib.nerfart_sdf_bwd2(p["surf_blob"], m, p["gbar_h7"], p["gbar_sdf"], p["f2_dump"], p["r2_dump"], null)),
+        "radiance_fwd_dump": (("rad_blob", "pts", "view", "nabla", "h7", "rgb_out", "dump"),
+                              lambda p, m: lib.nerfart_radiance_fwd_dump(p["rad_blob"], 1, p["pts"], p["view"], m, p["nabla"], p["h7"], p["rgb_out"],
+                                                                         p["dump"], null)),
+        "radiance_bwd": (("rad_blob", "rgb", "g_rgb", "fwd_dump", "bwd_dump", "g_h7_out", "g_n_out"),
+                         lambda p, m: lib.nerfart_radiance_bwd(p["rad_blob"], m, p["rgb"], p["g_rgb"], p["fwd_dump"], p["bwd_dump"], p["g_h7_out"],
+                                                               p["g_n_out"], null)),
+    }
+    for who, (names, call) in calls.items():
+        for bad in names:
+            ptrs = {n: (null if n == bad else one) for n in names}
+            assert call(ptrs, M) != 0, (who, bad)
+            assert who in err() and bad + " is NULL" in err(), (who, bad, err())
+        ptrs = {n: one for n in names}
+        for m in ((1 << 21) + 1, 1 << 30):
+            assert call(ptrs, m) != 0 and who in err() and "2^21" in err(), (who, m, err())
+        assert call(ptrs, -1) != 0 and "M out of range" in err()
+        assert call({n: null for n in names}, 0) == 0                               # no points: nothing to do
