@@ -582,6 +582,39 @@ int nerfart_mesh_simplify_count(const float* verts, const int* faces, unsigned V
 int nerfart_mesh_simplify_emit(const int* faces, unsigned V, unsigned F, int c, int nx, int ny, int nz, double reg, const void* ws, size_t ws_bytes,
                                const int* cluster, float* verts_out, int* faces_out, unsigned V_out, unsigned F_out, void* stream);
 
+/* ---- per-face texture atlas of an indexed mesh (csrc/mesh_texture.hip; mesh_util.texel_points / bake_texture / write_obj,
+ * extract_mesh(texture_model=)): where every texel of the atlas sits in space, and a Newton step that puts such points back onto the level set.
+ * Additions to ABI 5; no counterpart in the reference.  The colours are the caller's queries of the radiance net at these points.
+ * tests/mesh_texture_ref.py states all of this in numpy.
+ *   THE LAYOUT of F >= 1 faces at patch size P >= 1 (texel intervals along a triangle's legs): cell side S = P + 3; n_cells = ceil(F / 2); Cw the
+ *     smallest integer with Cw^2 >= n_cells; Ch = ceil(n_cells / Cw); image width W = Cw S, height H = Ch S, row 0 the TOP row.  Cell q sits at
+ *     column q % Cw, row q / Cw, and holds the faces 2 q (lower) and 2 q + 1 (upper).  Texel (x, y) has the cell (x / S, y / S) and the local
+ *     coordinates (i, j) = (x % S, y % S): with i + j <= P + 2 it belongs to the lower face with (a, b) = (i, j), otherwise to the upper face with
+ *     (a, b) = (S - 1 - i, S - 1 - j).  It is VALID iff its face index is < F (with an odd F the last upper half is not).
+ *   THE POINT of a valid texel: w1 = a / P, w2 = b / P, w0 = (P - a - b) / P (= 1 - w1 - w2; each one correctly rounded fp32 division of small
+ *     integers), p = fma(w2, v2, fma(w1, v1, w0 * v0)) per coordinate, v0 v1 v2 the face's vertices in face order.  The weights run from -2 / P
+ *     to (P + 2) / P: texels outside the triangle are the GUTTER, points of the face's plane at extrapolated barycentrics.
+ *   THE UVS (pixel units, texel centres at + 0.5, relative to the cell's origin): lower face (0.5, 0.5), (0.5 + P, 0.5), (0.5, 0.5 + P); upper
+ *     face S minus those.  With them, bilinear sampling at the UV of any point of a face (edges and corners included) reads, with non-zero
+ *     weight, only texels of that face, and texels carrying an affine function of their points return that function at the surface point.
+ *     OBJ's vt is u = X / W, v = 1 - Y / H.  Mip-mapping would read across cells: the atlas is for bilinear filtering at full resolution.
+ *   nerfart_mesh_atlas_layout: HOST only.  dims [5] (HOST) = {S, Cw, Ch, W, H}.  Refused with 2: P < 1, F < 1, W or H above 16384.
+ *   nerfart_mesh_atlas_points: verts [V, 3] fp32, faces [F, 3] int32; points [W H, 3] fp32 and face_of [W H] int32 in row-major texel order
+ *     (y W + x).  face_of = the owning face, -1 for an invalid texel, whose point is written as 0: every element of both arrays is written.
+ *     info [1] int32 (DEVICE) is zeroed, then set to 1 when a face holds an index outside [0, V): the texels of such a face are written as
+ *     invalid and nothing is read out of bounds.  One thread per texel, lanes along x, no atomics: two runs give the same bits.  Refusals as
+ *     the layout's, plus a null pointer and V >= 2^31.
+ *   nerfart_mesh_project_step: points [n, 3] in place, given sdf [n] and nabla [n, 3] at them: one Newton step toward sdf == level,
+ *     d = -(sdf - level) g / |g|^2, no longer than max_step.  Per point (fp32, every operation rounded once, in the order written):
+ *       1. sdf or a component of g not finite: the point stays.  g2 = fma(gz, gz, fma(gy, gy, gx * gx)); g2 < 1e-12 or not finite: it stays.
+ *       2. e = sdf - level;  gn = sqrt(g2);  m = min(|e| / gn, max_step);  c = copysign(m, -e) / gn;  c not finite: it stays.
+ *       3. p[k] = p[k] + c * g[k].
+ *     n == 0 launches nothing.  Refused with 2: a null pointer, max_step not positive. */
+int nerfart_mesh_atlas_layout(long long F, long long P, int* dims);
+int nerfart_mesh_atlas_points(const float* verts, const int* faces, unsigned V, unsigned F, int P, float* points, int* face_of, int* info,
+                              void* stream);
+int nerfart_mesh_project_step(float* points, const float* sdf, const float* nabla, unsigned n, float level, float max_step, void* stream);
+
 /* ---- narrow-band SDF sweep (csrc/mesh_band.hip; mesh_util.banded_volume, extract_mesh(narrow_band=True)): the device side of a sweep that
  * queries the SDF only in the bricks of the grid that can hold the isosurface.  Additions to ABI 5; no counterpart in the reference.  The SDF
  * queries themselves are the caller's: these entry points make points, keep per-brick flags and move values.

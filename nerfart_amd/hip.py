@@ -148,6 +148,9 @@ _SIGS = {
     "nerfart_mesh_simplify_workspace_bytes": (_ll, [_i, _i, _i, _i, _i, _i]),
     "nerfart_mesh_simplify_count": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _ll, _p, _p, _p]),
     "nerfart_mesh_simplify_emit": (_i, [_p, _i, _i, _i, _i, _i, _i, _d, _p, _ll, _p, _p, _p, _i, _i, _p]),
+    "nerfart_mesh_atlas_layout": (_i, [_ll, _ll, _p]),
+    "nerfart_mesh_atlas_points": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p]),
+    "nerfart_mesh_project_step": (_i, [_p, _p, _p, _i, _f, _f, _p]),
     "nerfart_band_workspace_bytes": (_ll, [_i, _i]),
     "nerfart_band_probe_points": (_i, [_i, _i, _d, _d, _p, _p]),
     "nerfart_band_select": (_i, [_i, _p, _f, _f, _i, _i, _p, _p, _p, _p, _p, _ll, _p, _p]),
@@ -518,6 +521,43 @@ def mesh_simplify_emit(verts, faces, dims, factor: int, reg: float, ws, cluster,
     _check(lib.nerfart_mesh_simplify_emit(fp, V, F, *grid, float(reg), _dev(ws, torch.uint8, "ws"), ws.numel(), _dev(cluster, torch.int32, "cluster"),
                                           out_v.data_ptr(), out_f.data_ptr(), int(V_out), int(F_out), _stream()), "nerfart_mesh_simplify_emit")
     return out_v, out_f
+
+
+def mesh_atlas_layout(F: int, P: int):
+    """nerfart_mesh_atlas_layout: (S, Cw, Ch, W, H) of the per-face texture atlas of F faces at patch size P (include/nerfart_hip.h); host only.
+    A refusal (F < 1, P < 1, an image side above 16384) raises with the library's message."""
+    dims = (C.c_int * 5)()
+    _check(lib.nerfart_mesh_atlas_layout(int(F), int(P), C.cast(dims, C.c_void_p)), "nerfart_mesh_atlas_layout")
+    return tuple(int(d) for d in dims)
+
+
+def mesh_atlas_points(verts, faces, P: int):
+    """nerfart_mesh_atlas_points on verts [V, 3] float32 and faces [F, 3] int32: (points [W * H, 3] float32, face_of [H, W] int32 - the owning face
+    of every texel, -1 for an invalid one, whose point is 0 -, info [1] int32 - 1 if a face holds an index outside [0, V)), all on verts' device.
+    No host synchronisation."""
+    if verts.dim() != 2 or verts.shape[1] != 3:
+        raise NerfartHipError(f"verts must be [V, 3] (got {tuple(verts.shape)})")
+    V = int(verts.shape[0])
+    vp = _dev(verts, name="verts")
+    fp, F = _mesh_faces(faces, V)
+    _, _, _, W, H = mesh_atlas_layout(F, P)                          # refuses before anything is allocated
+    points = torch.empty(W * H, 3, dtype=torch.float32, device=verts.device)
+    face_of = torch.empty(H, W, dtype=torch.int32, device=verts.device)
+    info = torch.empty(1, dtype=torch.int32, device=verts.device)
+    _check(lib.nerfart_mesh_atlas_points(vp, fp, V, F, int(P), points.data_ptr(), face_of.data_ptr(), info.data_ptr(), _stream()),
+           "nerfart_mesh_atlas_points")
+    return points, face_of, info
+
+
+def mesh_project_step(points, sdf, nabla, level: float, max_step: float):
+    """nerfart_mesh_project_step, in place on points [n, 3]: one Newton step toward sdf == level along nabla [n, 3], at most max_step long; a row
+    with a non-finite sdf or gradient, or |gradient|^2 < 1e-12, stays."""
+    n = int(points.shape[0])
+    if tuple(points.shape) != (n, 3) or tuple(sdf.shape) != (n,) or tuple(nabla.shape) != (n, 3):
+        raise NerfartHipError(f"mesh_project_step: points [{n}, 3], sdf [{n}], nabla [{n}, 3] expected (got {tuple(points.shape)}, {tuple(sdf.shape)}, "
+                              f"{tuple(nabla.shape)})")
+    _check(lib.nerfart_mesh_project_step(_dev(points, name="points"), _dev(sdf, name="sdf"), _dev(nabla, name="nabla"), n, float(level), float(max_step),
+                                         _stream()), "nerfart_mesh_project_step")
 
 
 def band_bricks(N: int, B: int) -> int:

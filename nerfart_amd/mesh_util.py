@@ -24,6 +24,9 @@ on the GPU (csrc/mesh_components.hip), `filter_components` keeps the largest one
 level set, the rest is filled with a value of the right sign, and the result checks and repairs itself (csrc/mesh_band.hip).
 `extract_mesh(simplify_factor=c)` decimates the mesh before it is written: `simplify_clusters` merges the vertices of every block of c^3 grid
 cells into one, placed by the quadric error metric of the block's faces (csrc/mesh_simplify.hip).
+`extract_mesh(texture_model=, filepath="*.obj")` writes a textured mesh - OBJ, MTL, PNG (`write_obj`) - instead of the PLY: `bake_texture` gives
+every face of the final mesh a patch of a per-face atlas and colours every texel at its own point, `texel_points` says where that is
+(csrc/mesh_texture.hip).
 """
 import numpy as np
 import torch
@@ -198,17 +201,25 @@ def quantize_colors(rgb):
 
 
 @torch.no_grad()
+def normal_view_radiance(model, pts):
+    """(normals [V, 3] float32, rgb [V, 3] float32) of a VolSDF / NeuS model at the points pts [V, 3] (the model's frame), V >= 1: the colour rule
+    of vertex_attributes before it is quantised - what the per-vertex colours and the texels of bake_texture share."""
+    from . import hip
+    view = -hip.normalize_dirs(model.implicit_surface.forward_with_nablas(pts)[1].contiguous())
+    rgb, _, nabla = model.forward(pts, view_dirs=view)
+    return hip.normalize_dirs(nabla.contiguous()), rgb
+
+
+@torch.no_grad()
 def vertex_attributes(model, pts):
     """(normals [V, 3] float32, colors [V, 3] uint8) of a VolSDF / NeuS model at the points pts [V, 3] (the model's frame).  The normal is
     hip.normalize_dirs(grad sdf) (F.normalize semantics); the colour is the radiance seen looking straight down the normal, view_dirs = -normal -
     the one choice without a free parameter.  Both are read from ONE model.forward(pts, view_dirs); the view direction it is handed needs the
     gradient first, which a query of the SDF net alone supplies (the same kernel on the same points: the same gradient)."""
-    from . import hip
     if pts.shape[0] == 0:
         return torch.zeros(0, 3, dtype=torch.float32, device=pts.device), torch.zeros(0, 3, dtype=torch.uint8, device=pts.device)
-    view = -hip.normalize_dirs(model.implicit_surface.forward_with_nablas(pts)[1].contiguous())
-    rgb, _, nabla = model.forward(pts, view_dirs=view)
-    return hip.normalize_dirs(nabla.contiguous()), quantize_colors(rgb)
+    normals, rgb = normal_view_radiance(model, pts)
+    return normals, quantize_colors(rgb)
 
 
 def mesh_components(faces, n_verts: int):
@@ -276,6 +287,137 @@ def simplify_clusters(verts_grid, faces, shape, factor, reg: float = 0.01):
     return out_v, out_f, cluster
 
 
+ATLAS_MAX_SIDE = 16384       # the largest image side of a texture atlas (csrc/mesh_texture.hip MAX_SIDE)
+TEXEL_CHUNK = 1 << 20        # texels per network query of texel_points / bake_texture
+
+
+def atlas_layout(F: int, patch: int):
+    """(S, Cw, Ch, W, H) of the per-face texture atlas of F faces at patch size `patch` - the closed form of include/nerfart_hip.h
+    (nerfart_mesh_atlas_layout gives the same five numbers): two faces per square cell of side S = patch + 3, Cw x Ch cells, image W x H.
+    ValueError: patch < 1, F < 1, an image side above ATLAS_MAX_SIDE."""
+    import math
+    F, P = int(F), int(patch)
+    if P < 1:
+        raise ValueError(f"atlas_layout: patch must be >= 1 (got {patch})")
+    if F < 1:
+        raise ValueError(f"atlas_layout: the mesh has no faces to texture (F = {F})")
+    S, cells = P + 3, (F + 1) // 2
+    Cw = math.isqrt(cells - 1) + 1                                  # the smallest integer with Cw^2 >= cells
+    Ch = (cells + Cw - 1) // Cw
+    if Cw * S > ATLAS_MAX_SIDE or Ch * S > ATLAS_MAX_SIDE:
+        raise ValueError(f"atlas_layout: F = {F} faces at patch P = {P} need an image of {Cw * S} x {Ch * S} texels, above the limit of "
+                         f"{ATLAS_MAX_SIDE} x {ATLAS_MAX_SIDE}: decimate the mesh first (simplify_factor) or use a smaller patch")
+    return S, Cw, Ch, Cw * S, Ch * S
+
+
+def atlas_uvs(F: int, patch: int):
+    """[F, 3, 2] float64 numpy: the UV of every face corner in PIXEL units (x to the right, y down from the top row, texel centres at + 0.5).  In
+    its cell the lower face 2 q has (0.5, 0.5), (0.5 + P, 0.5), (0.5, 0.5 + P), the upper face 2 q + 1 has S minus those; the cell's origin is
+    ((q % Cw) S, (q // Cw) S).  Closed form: no kernel."""
+    S, Cw, _, _, _ = atlas_layout(F, patch)
+    P = int(patch)
+    f = np.arange(int(F))
+    q = f // 2
+    origin = np.stack([(q % Cw) * S, (q // Cw) * S], axis=-1).astype(np.float64)[:, None, :]
+    lower = np.array([[0.5, 0.5], [0.5 + P, 0.5], [0.5, 0.5 + P]], dtype=np.float64)
+    local = np.where((f % 2 == 0)[:, None, None], lower[None], S - lower[None])
+    return origin + local
+
+
+@torch.no_grad()
+def texel_points(verts, faces, patch: int, query_fn=None, project: int = 0, level: float = 0.0, max_step: float = None):
+    """Where every texel of the atlas of the mesh (verts [V, 3] float32, faces [F, 3] int32, on the GPU) sits in space (csrc/mesh_texture.hip; the
+    rules are in include/nerfart_hip.h): (points [H * W, 3] float32, face_of [H, W] int32), on the GPU, rows in texel order y W + x.  face_of is
+    the owning face, -1 for a texel no face owns (its point is 0).  A texel outside its triangle - the gutter bilinear filtering reads - is a
+    point of the face's plane at extrapolated barycentrics.
+
+    project = k > 0 moves every valid texel k Newton steps toward sdf == level, each at most max_step long: query_fn(pts [M, 3]) ->
+    (sdf [M], nabla [M, 3], ...) is asked in chunks of at most TEXEL_CHUNK points (hip.mesh_project_step).  A face of a decimated mesh is a
+    chord of the true surface; this puts its texels back where the radiance net was trained.  One host read (the flag).
+    ValueError: a face index outside [0, V), patch < 1, no faces, an atlas above the size limit, project < 0, project > 0 without query_fn or
+    a positive max_step.  CPU tensors are refused: there is no CPU path."""
+    from . import hip
+    project = int(project)
+    if project < 0:
+        raise ValueError(f"texel_points: project must be >= 0 (got {project})")
+    if project > 0 and (query_fn is None or max_step is None or not float(max_step) > 0.0):
+        raise ValueError(f"texel_points: project = {project} needs query_fn and a positive max_step (got query_fn = {query_fn}, max_step = {max_step})")
+    if not (torch.is_tensor(faces) and faces.dim() == 2 and faces.shape[1] == 3):
+        raise ValueError("texel_points: faces must be a tensor [F, 3]")
+    atlas_layout(int(faces.shape[0]), patch)                        # ValueError before anything is allocated
+    points, face_of, info = hip.mesh_atlas_points(verts, faces, int(patch))
+    if int(info.cpu()[0]):
+        raise ValueError(f"texel_points: a face holds a vertex index outside [0, {int(verts.shape[0])})")
+    if project > 0:
+        valid = torch.nonzero(face_of.reshape(-1) >= 0).reshape(-1)
+        pts = points[valid]
+        for _ in range(project):
+            for s in range(0, pts.shape[0], TEXEL_CHUNK):
+                part = pts[s:s + TEXEL_CHUNK]                       # a view: the step is taken in place
+                out = query_fn(part)
+                hip.mesh_project_step(part, out[0].reshape(-1).contiguous(), out[1].reshape(-1, 3).contiguous(), level, max_step)
+        points[valid] = pts
+    return points, face_of
+
+
+@torch.no_grad()
+def bake_texture(verts, faces, color_fn, patch: int = 4, query_fn=None, project: int = 0, level: float = 0.0, max_step: float = None):
+    """The texture of the mesh (verts [V, 3], faces [F, 3] int32, on the GPU): (image [H, W, 3] uint8 on the GPU, uv [F, 3, 2] float64 numpy in pixel
+    units = atlas_uvs(F, patch)).  Every valid texel is quantize_colors(color_fn(its point)) - color_fn(pts [M, 3]) -> rgb [M, 3] is asked in
+    chunks of at most TEXEL_CHUNK points, at texel_points(verts, faces, patch, query_fn, project, level, max_step) -, every other texel is 0.
+    Bilinear sampling at a face's UVs reads that face's texels only, and reproduces a colour that is affine over the face exactly (up to the
+    quantisation): no dilation pass is needed.  Mip-mapping would mix neighbouring cells."""
+    points, face_of = texel_points(verts, faces, patch, query_fn=query_fn, project=project, level=level, max_step=max_step)
+    H, W = face_of.shape
+    valid = torch.nonzero(face_of.reshape(-1) >= 0).reshape(-1)
+    pts = points[valid]
+    image = torch.zeros(H * W, 3, dtype=torch.uint8, device=points.device)
+    image[valid] = torch.cat([quantize_colors(color_fn(pts[s:s + TEXEL_CHUNK]).reshape(-1, 3)) for s in range(0, pts.shape[0], TEXEL_CHUNK)])
+    return image.reshape(H, W, 3), atlas_uvs(int(faces.shape[0]), patch)
+
+
+def write_obj(path, verts, faces, uv, image, normals=None):
+    """Wavefront OBJ with a material and a texture: writes <stem>.obj, <stem>.mtl and <stem>.png next to each other (path must end in .obj) and
+    returns path.  verts [V, 3], faces [F, 3], normals [V, 3] or None: tensors or arrays; uv [F, 3, 2] in PIXEL units of image [H, W, 3] uint8
+    (atlas_uvs: y down from the top row).  The OBJ holds `mtllib`, `usemtl`, V `v` lines, 3 F `vt` lines (u = X / W, v = 1 - Y / H: OBJ's v
+    runs up from the bottom row), V `vn` lines if normals are given, and F faces `f v/vt` or `f v/vt/vn`, all indices 1-based; the MTL
+    `newmtl` and `map_Kd <stem>.png`; the PNG is written with PIL.  Floats are printed with %.9g: enough digits to give every fp32 back."""
+    import os
+    from PIL import Image
+    host = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    path = str(path)
+    if not path.endswith(".obj"):
+        raise ValueError(f"write_obj: the path must end in .obj (got {path!r})")
+    v = host(verts).reshape(-1, 3)
+    f = host(faces).reshape(-1, 3).astype(np.int64)
+    img = np.ascontiguousarray(host(image))
+    uv = np.asarray(host(uv), dtype=np.float64)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError(f"write_obj: image must be uint8 [H, W, 3] (got {img.dtype} {img.shape})")
+    if uv.shape != (len(f), 3, 2):
+        raise ValueError(f"write_obj: uv must be [{len(f)}, 3, 2] (got {uv.shape})")
+    n = None if normals is None else host(normals)
+    if n is not None and n.shape != (len(v), 3):
+        raise ValueError(f"write_obj: normals must be [{len(v)}, 3] (got {n.shape})")
+    H, W = img.shape[:2]
+    stem = path[:-len(".obj")]
+    name = os.path.basename(stem)
+    lines = [f"mtllib {name}.mtl", f"usemtl {name}"]
+    lines += ["v %.9g %.9g %.9g" % tuple(float(c) for c in p) for p in v]
+    lines += ["vt %.9g %.9g" % (x / W, 1.0 - y / H) for x, y in uv.reshape(-1, 2)]
+    if n is not None:
+        lines += ["vn %.9g %.9g %.9g" % tuple(float(c) for c in p) for p in n]
+        lines += ["f " + " ".join(f"{int(a) + 1}/{3 * k + c + 1}/{int(a) + 1}" for c, a in enumerate(tri)) for k, tri in enumerate(f)]
+    else:
+        lines += ["f " + " ".join(f"{int(a) + 1}/{3 * k + c + 1}" for c, a in enumerate(tri)) for k, tri in enumerate(f)]
+    with open(path, "w") as out:
+        out.write("\n".join(lines) + "\n")
+    with open(stem + ".mtl", "w") as out:
+        out.write(f"newmtl {name}\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {name}.png\n")
+    Image.fromarray(img).save(stem + ".png")
+    return path
+
+
 def write_ply(path, verts, faces, normals=None, colors=None):
     """Binary little-endian PLY: `element vertex` with float x, y, z and `element face` with `property list uchar int vertex_indices` - the file
     plyfile writes for the reference's two elements (mesh_util.py:57-80).  verts [V, 3], faces [F, 3]: tensors or arrays.  Optional per-vertex
@@ -317,13 +459,24 @@ def write_ply(path, verts, faces, normals=None, colors=None):
 @torch.no_grad()
 def _extract_mesh_with_vertex_data(implicit_surface, volume_size, level, N, filepath, chunk, refine_evals, vertex_normals, color_model,
                                    keep_largest=None, min_component_faces=None, narrow_band=False, band_brick=8, band_lipschitz=BAND_LIPSCHITZ,
-                                   band_info=None, simplify_factor=None, simplify_reg=0.01):
-    """extract_mesh with any of refine_evals / vertex_normals / color_model / simplify_factor set: every vertex is (edge, t); positions are written
+                                   band_info=None, simplify_factor=None, simplify_reg=0.01, texture_model=None, texture_patch=4, texture_project=0):
+    """extract_mesh with any of refine_evals / vertex_normals / color_model / simplify_factor / texture_model set: every vertex is (edge, t); positions are written
     in the placement frame, every network query is made in the model's frame, so the refinement does not depend on how the mesh is placed.
     Without simplify_factor components are dropped once, at the end, from positions, faces, normals and colours together.  With it the
     (refined) vertices are taken in grid coordinates, floaters go first - before clustering can weld them to the surface -, simplify_clusters
-    merges the rest, and normals and colours are queried at the NEW vertices only."""
+    merges the rest, and normals and colours are queried at the NEW vertices only.  With texture_model the bake comes last, on the final mesh in
+    the model's frame (bake_texture), and the mesh is written as OBJ + MTL + PNG instead of PLY."""
     from . import hip
+
+    def write(verts, faces, normals, colors, model_pts):
+        """The file: PLY, or with texture_model the textured OBJ - model_pts() gives the final vertices in the model's frame."""
+        if texture_model is None:
+            return write_ply(filepath, verts, faces, normals, colors)
+        image, uv = bake_texture(model_pts(), faces, lambda p: normal_view_radiance(texture_model, p)[1], patch=texture_patch,
+                                 query_fn=implicit_surface.forward_with_nablas, project=texture_project, level=level,
+                                 max_step=(simplify_factor or 1) * volume_size / N)
+        return write_obj(filepath, verts, faces, uv, image, normals)
+
     if refine_evals < 0:
         raise ValueError(f"extract_mesh: refine_evals must be >= 0 (got {refine_evals})")
     vol = (sdf_volume(implicit_surface, volume_size, N, chunk, narrow_band=True, band_brick=band_brick, band_lipschitz=band_lipschitz, level=level,
@@ -352,23 +505,29 @@ def _extract_mesh_with_vertex_data(implicit_surface, volume_size, level, N, file
                 normals, colors = vertex_attributes(color_model, pts)
             else:
                 normals = hip.normalize_dirs(implicit_surface.forward_with_nablas(pts)[1].contiguous()) if pts.shape[0] else pts
-        return write_ply(filepath, verts, faces, normals if vertex_normals else None, colors)
+        return write(verts, faces, normals if vertex_normals else None, colors, lambda: grid_to_frame(grid, *model_frame(N, volume_size)))
     if vertex_normals or color_model is not None:
         pts = hip.mesh_edge_points(edge, t, vol.shape, *model_frame(N, volume_size))
         if color_model is not None:
             normals, colors = vertex_attributes(color_model, pts)
         else:
             normals = hip.normalize_dirs(implicit_surface.forward_with_nablas(pts)[1].contiguous()) if V else pts
+    src = None
     if keep_largest is not None or min_component_faces is not None:
         verts, faces, src = filter_components(verts, faces, keep_largest, min_component_faces)
         normals, colors = (a if a is None else a[src.long()] for a in (normals, colors))
-    return write_ply(filepath, verts, faces, normals if vertex_normals else None, colors)
+
+    def model_pts():
+        pts = hip.mesh_edge_points(edge, t, vol.shape, *model_frame(N, volume_size))
+        return pts if src is None else pts[src.long()]
+    return write(verts, faces, normals if vertex_normals else None, colors, model_pts)
 
 
 def extract_mesh(implicit_surface, volume_size=2.0, level=0.0, N=512, filepath="./surface.ply", show_progress=True, chunk=1 << 24,
                  reference_shear: bool = False, backend: str = "native", refine_evals: int = 0, vertex_normals: bool = False, color_model=None,
                  keep_largest: int = None, min_component_faces: int = None, narrow_band: bool = False, band_brick: int = 8,
-                 band_lipschitz: float = BAND_LIPSCHITZ, band_info: dict = None, simplify_factor: int = None, simplify_reg: float = 0.01):
+                 band_lipschitz: float = BAND_LIPSCHITZ, band_info: dict = None, simplify_factor: int = None, simplify_reg: float = 0.01,
+                 texture_model=None, texture_patch: int = 4, texture_project: int = 0):
     """mesh_util.extract_mesh: SDF volume -> marching cubes -> .ply.  backend="native" (default): marching_cubes + write_ply above, nothing
     third-party, the volume stays on the GPU; backend="skimage": the reference's route (needs scikit-image and plyfile).  Both place the mesh as
     the reference does: spacing volume_size / N, offset -volume_size / 2 (mesh_util.py:112).  reference_shear=True samples
@@ -395,7 +554,28 @@ def extract_mesh(implicit_surface, volume_size=2.0, level=0.0, N=512, filepath="
     into one, placed by the quadrics of the block's faces (simplify_clusters; csrc/mesh_simplify.hip; simplify_reg pulls it toward the members'
     mean): roughly c^2 times fewer triangles.  The order is marching cubes, refinement, keep_largest / min_component_faces, clustering, and only
     then vertex_normals / color_model, queried at the new vertices.  ValueError with reference_shear=True (the clusters are blocks of the regular
-    lattice) and with backend="skimage" (the clustering runs on the GPU, on the native extractor's vertices)."""
+    lattice) and with backend="skimage" (the clustering runs on the GPU, on the native extractor's vertices).
+
+    texture_model (the whole VolSDF / NeuS model; native backend, regular grid; None: the paths above, untouched) writes a textured mesh instead
+    of a PLY: filepath must end in .obj, and <stem>.obj, <stem>.mtl and <stem>.png are written (write_obj); the .obj path is returned.  The bake
+    runs last - marching cubes, refinement, keep_largest / min_component_faces, clustering, then bake_texture on the final mesh in the model's
+    frame: every face owns a patch of texture_patch texel intervals along its legs in a per-face atlas, every texel is vertex_attributes'
+    colour rule (the radiance looking down the normal) at the texel's own point.  texture_project = k moves the texels k Newton steps onto the
+    level set first, each at most (simplify_factor or 1) * volume_size / N long - a decimated face is a chord of the surface.  vertex_normals
+    become the OBJ's vn.  ValueError: a path not ending in .obj, color_model as well (OBJ has no standard vertex colours), reference_shear=True,
+    backend="skimage", a mesh without faces or one whose atlas would pass 16384 texels a side (use simplify_factor or a smaller patch)."""
+    if texture_model is not None:
+        if not str(filepath).endswith(".obj"):
+            raise ValueError(f"extract_mesh: texture_model writes OBJ + MTL + PNG: filepath must end in .obj (got {filepath!r})")
+        if color_model is not None:
+            raise ValueError("extract_mesh: texture_model and color_model exclude each other (OBJ has no standard vertex colours)")
+        if reference_shear:
+            raise ValueError("extract_mesh: texture_model needs the regular grid (reference_shear=True samples a sheared lattice, which has no "
+                             "regular frame to query the model in)")
+        if backend == "skimage":
+            raise ValueError("extract_mesh: texture_model needs backend='native' (the atlas is baked on the GPU, on the native extractor's mesh)")
+        if int(texture_patch) < 1 or int(texture_project) < 0:
+            raise ValueError(f"extract_mesh: texture_patch must be >= 1 and texture_project >= 0 (got {texture_patch}, {texture_project})")
     if simplify_factor is not None and reference_shear:
         raise ValueError("extract_mesh: simplify_factor needs the regular grid (reference_shear=True samples a sheared lattice, whose cells are not "
                          "the blocks the clusters are made of)")
@@ -410,13 +590,13 @@ def extract_mesh(implicit_surface, volume_size=2.0, level=0.0, N=512, filepath="
     filtering = keep_largest is not None or min_component_faces is not None
     if filtering and backend != "native":
         raise ValueError("extract_mesh: keep_largest / min_component_faces need backend='native' (the components are found on the GPU)")
-    if refine_evals or vertex_normals or color_model is not None or simplify_factor is not None:
+    if refine_evals or vertex_normals or color_model is not None or simplify_factor is not None or texture_model is not None:
         if reference_shear or backend != "native":
             raise ValueError("extract_mesh: refine_evals / vertex_normals / color_model need backend='native' and the regular grid "
                              "(the sheared grid has no regular frame, scikit-image gives no edge table)")
         return _extract_mesh_with_vertex_data(implicit_surface, volume_size, level, N, filepath, chunk, int(refine_evals), vertex_normals, color_model,
                                               keep_largest, min_component_faces, narrow_band, band_brick, band_lipschitz, band_info,
-                                              simplify_factor, simplify_reg)
+                                              simplify_factor, simplify_reg, texture_model, int(texture_patch), int(texture_project))
     if backend == "native":
         vol = (sdf_volume(implicit_surface, volume_size, N, chunk, narrow_band=True, band_brick=band_brick, band_lipschitz=band_lipschitz,
                           level=level, band_info=band_info) if narrow_band

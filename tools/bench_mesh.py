@@ -5,8 +5,11 @@ JSON line (NOT the driver's bench contract - that is bench.py).  Per-kernel time
 under `rocprofv3 --kernel-trace --stats` with --no-sdf.  `--narrow_band [--band_brick B]` adds, in the same job, the narrow-band sweep's median
 time (banded_volume_ms, beside the dense sdf_volume_ms), the share of grid points it queried, its repair rounds and whether marching cubes gives
 the dense sweep's mesh bit for bit.  `--simplify C` adds the simplify stage on the same mesh: mesh_util.simplify_clusters' median time, its two
-halves (nerfart_mesh_simplify_count, _emit) and V, F -> V', F'.  DESIGN.md 4.7 says which of these figures have been taken."""
-import argparse, json, os, statistics, sys
+halves (nerfart_mesh_simplify_count, _emit) and V, F -> V', F'.  `--texture P [--texture_project K]` adds the texture bake of that mesh (the
+simplified one with --simplify, else marching cubes' own) in the model's frame: nerfart_mesh_atlas_points, the K projection steps (SDF + gradient
+queries and nerfart_mesh_project_step; the step kernel also alone), the colour queries, mesh_util.bake_texture as a whole, and - once, on the
+host's clock - mesh_util.write_obj.  DESIGN.md 4.7 says which of these figures have been taken."""
+import argparse, json, os, statistics, sys, tempfile, time
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -33,6 +36,8 @@ def main():
     ap.add_argument("--narrow_band", action="store_true", help="also time the narrow-band sweep (mesh_util.banded_volume) and compare its mesh")
     ap.add_argument("--band_brick", type=int, default=8)
     ap.add_argument("--simplify", type=int, default=None, help="also time mesh_util.simplify_clusters with this cluster factor on the extracted mesh")
+    ap.add_argument("--texture", type=int, default=None, help="also time the texture bake (mesh_util.bake_texture) with this patch size")
+    ap.add_argument("--texture_project", type=int, default=2, help="projection steps of --texture")
     args = ap.parse_args()
     from nerfart_amd import scene, mesh_util, hip
     dev = torch.device("cuda", 0)
@@ -76,6 +81,44 @@ def main():
                                            args.iters)
         res.update(simplify_factor=c, simplified_vertices=int(out_v.shape[0]), simplified_triangles=int(out_f.shape[0]),
                    simplify_workspace_MiB=round(sws.numel() / 2 ** 20, 1))
+    if args.texture:                                               # the bake of the final mesh, in the model's frame
+        P, K, c = args.texture, args.texture_project, args.simplify or 1
+        if args.simplify:
+            tverts, tfaces = mesh_util.grid_to_frame(out_v, *mesh_util.model_frame(N, vs)), out_f
+        else:
+            tverts, tfaces = hip.mc_emit(vol, 0.0, *mesh_util.model_frame(N, vs), ws, V, F)
+        surface, max_step, chunk = model.implicit_surface, c * vs / N, mesh_util.TEXEL_CHUNK
+        S, Cw, Ch, W, H = hip.mesh_atlas_layout(tfaces.shape[0], P)
+        points, face_of, _ = hip.mesh_atlas_points(tverts, tfaces, P)                           # warm-up
+        res["texture_points_ms"], _ = timed(lambda: hip.mesh_atlas_points(tverts, tfaces, P), args.iters)
+        start = torch.nonzero(face_of.reshape(-1) >= 0).reshape(-1)
+        start = points[start]
+        parts = lambda p: [p[s:s + chunk] for s in range(0, p.shape[0], chunk)]
+
+        def project():
+            p = start.clone()
+            for _ in range(K):
+                for part in parts(p):
+                    sdf, nabla = surface.forward_with_nablas(part)[:2]
+                    hip.mesh_project_step(part, sdf.reshape(-1).contiguous(), nabla.reshape(-1, 3).contiguous(), 0.0, max_step)
+            return p
+        color = lambda p: [mesh_util.quantize_colors(mesh_util.normal_view_radiance(model, part)[1]) for part in parts(p)]
+        at = project()                                             # warm-ups
+        color(at)
+        res["texture_project_ms"], _ = timed(project, max(3, args.iters // 4))
+        queried = [(part, *(t.contiguous() for t in surface.forward_with_nablas(part)[:2])) for part in parts(start.clone())]
+        res["texture_project_step_kernel_ms"], _ = timed(lambda: [hip.mesh_project_step(p_, s_, n_, 0.0, max_step) for p_, s_, n_ in queried], args.iters)
+        res["texture_color_ms"], _ = timed(lambda: color(at), max(3, args.iters // 4))
+        bake = lambda: mesh_util.bake_texture(tverts, tfaces, lambda p: mesh_util.normal_view_radiance(model, p)[1], patch=P,
+                                              query_fn=surface.forward_with_nablas, project=K, level=0.0, max_step=max_step)
+        res["texture_bake_ms"], (image, uv) = timed(bake, max(3, args.iters // 4))
+        with tempfile.TemporaryDirectory() as tmp:
+            t0 = time.perf_counter()
+            mesh_util.write_obj(os.path.join(tmp, "bench.obj"), tverts, tfaces, uv, image)
+            res["texture_write_obj_s"] = round(time.perf_counter() - t0, 2)
+            res["texture_png_MiB"] = round(os.path.getsize(os.path.join(tmp, "bench.png")) / 2 ** 20, 2)
+        res.update(texture_patch=P, texture_project=K, texture_faces=int(tfaces.shape[0]), texture_image=[W, H], texture_valid_texels=int(start.shape[0]),
+                   texture_points_bytes=W * H * 16 + int(tfaces.shape[0]) * 12)      # written per texel: 12 + 4; the faces read once (vertices from cache)
     print(json.dumps(res))
 
 

@@ -9,7 +9,10 @@ colours to the file; without them the file is the reference's two elements.  `--
 largest connected components of the surface are written.  `--narrow_band [--band_brick B --band_lipschitz L]` sweeps the SDF only near the surface
 (mesh_util.banded_volume; the same file when L bounds |grad sdf|) and prints the sweep's counts as one JSON line.  `--simplify C [--simplify_reg R]`
 decimates the mesh on the GPU before it is written: the vertices of every block of C^3 grid cells become one, placed by the quadric error metric of
-the block's faces (mesh_util.simplify_clusters), after the floaters are gone and before normals and colours are queried.  Without --load_pt the mesh is the model's sphere initialisation.  `--k1:k2 v` overrides of the config work as everywhere (nerfart_amd.config)."""
+the block's faces (mesh_util.simplify_clusters), after the floaters are gone and before normals and colours are queried.  `--texture
+[--texture_patch P --texture_project K]` with `--out mesh.obj` writes a textured mesh instead of a PLY - mesh.obj, mesh.mtl, mesh.png: every face
+of the final mesh gets a patch of P texel intervals along its legs in a per-face atlas, baked on the GPU from the radiance net looking down the
+normal (mesh_util.bake_texture); K Newton steps put the texels of a decimated face back onto the surface first.  Without --load_pt the mesh is the model's sphere initialisation.  `--k1:k2 v` overrides of the config work as everywhere (nerfart_amd.config)."""
 import json
 import os
 import sys
@@ -47,6 +50,11 @@ def parse(argv=None):
                                                                    "C^2 times fewer triangles")
     parser.add_argument("--simplify_reg", type=float, default=0.01, help="how strongly --simplify pulls a merged vertex toward the mean of its members "
                                                                          "where the faces' planes do not fix it")
+    parser.add_argument("--texture", action="store_true", help="write a textured mesh, <out>.obj + .mtl + .png (--out must end in .obj), instead of "
+                                                               "a PLY: a per-face atlas baked from the radiance net; not together with --colors")
+    parser.add_argument("--texture_patch", type=int, default=4, help="texel intervals along a triangle's legs in the atlas of --texture (>= 1)")
+    parser.add_argument("--texture_project", type=int, default=0, help="Newton steps that move the texels of --texture onto the level set before "
+                                                                       "they are coloured (2 is plenty after --simplify)")
     args, unknown = parser.parse_known_args(argv)
     return args, cfg.load_config(args, unknown)
 
@@ -66,7 +74,8 @@ def main():
                                   refine_evals=args.refine, vertex_normals=args.normals, color_model=model if args.colors else None,
                                   keep_largest=args.keep_largest, min_component_faces=args.min_faces, narrow_band=args.narrow_band,
                                   band_brick=args.band_brick, band_lipschitz=args.band_lipschitz, band_info=info, simplify_factor=args.simplify,
-                                  simplify_reg=args.simplify_reg)
+                                  simplify_reg=args.simplify_reg, texture_model=model if args.texture else None, texture_patch=args.texture_patch,
+                                  texture_project=args.texture_project)
     if args.narrow_band:
         print(json.dumps(info))
     print(path)
