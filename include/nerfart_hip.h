@@ -758,7 +758,28 @@ int nerfart_wgrad_operand_sbar_ones(const float* sbar, long long M, long long ro
  *   for the SDF net's layers 0..8, then the radiance net's 0..4; offsets in floats, last = total (returned).  multires = the SDF
  *   net's embed_multires (6), multires_view = the radiance net's embed_multires_view (-1 | 4).
  * nerfart_weight_norm_bwd: nn.utils.weight_norm's chain rule for one layer (models/base.py:226-227): dW [out, in] ->
- *   g_weight_v [out, in], g_weight_g [out] (either may be NULL; accumulate != 0 adds to them). */
+ *   g_weight_v [out, in], g_weight_g [out] (either may be NULL; accumulate != 0 adds to them).
+ *
+ * The raw buffer, slot by slot (tests/param_grad_ref.py holds every element of it to fp64 products of the dumps and operands; unit order
+ * throughout; Mp = the padded point count of the dumps):
+ *   - EVERY call ADDS to the sections it reduces into - nerfart_sdf_param_bwd: sections 0..5; nerfart_radiance_param_bwd: 6..11; the ray-level
+ *     calls: all of them - and touches no other section.  Two calls over disjoint halves of the points give the sums of one call over all of
+ *     them (not the same bits: the padding differs).
+ *   - written and never read: row 1 of SURF_CS0 (the column sums of zbar_4 once more: the bias of layer 4 is folded from SURF_CS17); the rows
+ *     (SURF_WW[2], SURF_CS17[2]) and columns (SURF_WW[3]) at the unit positions of features 217..255 of SDF layer 3, which has 217 outputs
+ *     (finite: products of whatever the dumps hold there).
+ *   - only zero is added, never read: the columns of the 64-wide sections that no operand column fills (SURF_WE 39..63; SURF_W8 1..31,
+ *     33..63; RAD_W4 3..31, 35..63; RAD_WEX nex..31, 32 + nex..63 for nex = 9, 33..63 for nex = 33).  The reduction runs over all 64 columns
+ *     and the operands hold 0 there, so each call rewrites them as old + 0: the value is kept (a -0 becomes +0) as long as the dumps are finite.
+ *   - never written, never read: SURF_B8[1..3], RAD_B4[3].
+ *   - nerfart_fold_weight_grads reads none of the slots of the last three items (NaN there does not reach `folded`) and writes every
+ *     element of `folded` up to offsets[28], nothing behind it.
+ *   - train_radiance == 0: only RAD_WH7 and row 4 of RAD_CS (the geometry-feature rows of the last SDF layer and their bias) are added to,
+ *     with the same bits as with train_radiance != 0; RAD_WW, rows 0..3 of RAD_CS, RAD_W4, RAD_B4 and RAD_WEX are left untouched.
+ *   - after the radiance-only route (nerfart_radiance_param_bwd into a zeroed buffer) SURF_W8 and SURF_B8 are 0, so row 0 of dW_8 - the sdf
+ *     row of the last SDF layer - its bias entry and their weight_norm gradients come out exactly 0.
+ *   - the scalars d loss / d alpha, d beta, d s are sums over the rays formed with atomicAdd (one value per ray, k_composite_*_bwd): no fixed
+ *     summation order, so two runs may differ in the last bit.  Every other slot is bit-reproducible; the eikonal scalar is a two-stage sum. */
 long long nerfart_pass2_raw_layout(long long* offsets);
 long long nerfart_volsdf_render_bwd_workspace_bytes(int n_rays, int P, int have_state);
 int nerfart_volsdf_render_bwd(const float* surf_blob, const float* rad_blob, int view_tiles, int multires, const float* rays_o, const float* rays_d,
