@@ -615,6 +615,67 @@ int nerfart_mesh_atlas_points(const float* verts, const int* faces, unsigned V, 
                               void* stream);
 int nerfart_mesh_project_step(float* points, const float* sdf, const float* nabla, unsigned n, float level, float max_step, void* stream);
 
+/* ---- rasteriser for an indexed mesh (csrc/mesh_raster.hip; mesh_util.rasterize / render_mesh, tools/render_mesh.py): what a rend_util.get_rays
+ * camera sees of the mesh extract_mesh wrote.  Additions to ABI 5; no counterpart in the reference.  Every decision is an integer, every float
+ * result is computed once in the order written here, and nothing depends on the order of work: tests/mesh_raster_ref.py states all of this in
+ * numpy and the GPU tests compare for equality.
+ *   THE CAMERA: c2w is a 4x4 row-major OpenCV camera; the HOST inverts it in float64 and passes w2c [12] (the 3x4, rounded to fp32 once), rot [9]
+ *     (c2w's rotation) and K5 [5] = (fx, sk, cx, fy, cy) = K[0], K[1], K[2], K[5], K[6] of the 4x4 K, as k_get_rays reads it - all HOST arrays.
+ *     Pixel (column i, row j) is sampled at its integer coordinates, NO half-pixel offset, index j W + i (csrc/raygen.hip).  A camera-space
+ *     point (X, Y, Z) projects to u = fx X/Z + sk Y/Z + cx, v = fy Y/Z + cy: the inverse of lift.  The ray of pixel (i, j) is r = (x, y, 1),
+ *     x = ((i - cx + cy sk / fy) - sk j / fy) / fx, y = (j - cy) / fy: k_get_rays' expressions.  All of it in double from the fp32 numbers,
+ *     every operation rounded once (no fma), sums left to right.
+ *   nerfart_mesh_project, one thread per vertex: (X, Y, Z) = w2c (p, 1) per row ((m0 px + m1 py) + m2 pz) + m3; xz = X / Z, yz = Y / Z;
+ *     u = (fx xz + sk yz) + cx, v = fy yz + cy.  The vertex is INVALID when NOT Z >= near (NaN included) or NOT |u| <= 2^15 or NOT |v| <= 2^15.
+ *     xy_fix [V, 2] int32 = rint(256 u), rint(256 v) (round half to even; 8 sub-pixel bits; 0 0 for an invalid vertex); cam [V, 3] fp32 = the
+ *     double (X, Y, Z) rounded once (written for every vertex); valid [V] uint8.
+ *   nerfart_mesh_raster: sets zbuf [H W] uint64 to all ones and info [4] int32 to 0 on the caller's stream, then per face:
+ *       1. an index outside [0, V): info[0] = 1, the face is skipped.
+ *       2. an invalid vertex: the face is skipped WHOLE and counted in info[1] (integer atomic).  THERE IS NO POLYGON CLIPPING: a face that
+ *          crosses the near plane, or reaches beyond 2^15 pixels, is not drawn at all.
+ *       3. A = (x1 - x0)(y2 - y0) - (y1 - y0)(x2 - x0) in int64 from xy_fix; A == 0: skipped.  A < 0: corners 1 and 2 are swapped, so that
+ *          A > 0 (both orientations are drawn; there is no back-face culling).
+ *       4. COVERAGE of pixel (i, j), sample s = (256 i, 256 j): for each directed edge a -> b of (0 1, 1 2, 2 0),
+ *          E = (xb - xa)(sy - ya) - (yb - ya)(sx - xa) in int64 (|coordinate| <= 2^23, |difference| <= 2^24, |product| <= 2^48).  The pixel
+ *          is covered iff for every edge E > 0, or E == 0 and the edge is a TOP or LEFT edge.  y runs down and A > 0, so the corners run
+ *          clockwise on screen: TOP is yb == ya and xb > xa (horizontal, the face below it), LEFT is yb < ya (running up, the face to its
+ *          right).  A sample on an edge two faces share belongs to exactly one of them; nothing about coverage is floating point.
+ *       5. at a covered pixel, in double: n = (b - a) x (c - a) from the three cam vertices in the face's own order (fp32 values, unsnapped),
+ *          z = ((nx ax + ny ay) + nz az) / ((nx x + ny y) + nz).  NOT z >= near, or z not finite: nothing is written, info[2] counts it.
+ *       6. key = (bits(float(z)) << 32) | face, atomicMin on unsigned long long.  z > 0, so the bit patterns order as the floats do; equal
+ *          depths go to the smaller face index; the winner does not depend on the order of the faces.  No float atomics.
+ *     Work: one thread per face; the clipped box i in [ceil(xmin / 256), floor(xmax / 256)] x the same in j, cut to the image, is walked by that
+ *     thread when it holds at most 256 pixels; otherwise the face is appended to list [F] int32 (integer atomic, info[3] counts; the image
+ *     does not depend on the list's order) and a second launch works the list one workgroup per face, threads across the box.
+ *   nerfart_mesh_resolve, one thread per pixel, lanes along x: face = low word of the key, -1 for all ones.  z as in 5 (the same bits), the hit
+ *     point h = z r, and the barycentrics as signed areas against the face's own normal:
+ *       w0 = n . ((b - h) x (c - h)) / (n . n),  w1 = n . ((c - h) x (a - h)) / (n . n),  w2 = n . ((a - h) x (b - h)) / (n . n).
+ *     They may leave [0, 1] by what the 1/256-pixel snap allows - harmless: the atlas's gutter texels exist for extrapolated weights.
+ *     Outputs, each rounded to fp32 once: face_id [H W] int32, bary [H W, 3], z [H W], depth [H W] = z sqrt((x x + y y) + 1) - the distance
+ *     along the UNIT ray, which is what render_fn's depth_volume and surface_render's depths are (both normalise rays_d before they march) -,
+ *     mask [H W] uint8, normals [H W, 3] = rot (s n / |n|) with s = -1 if n . r > 0 else 1: the geometric normal in world space, turned
+ *     toward the camera.  A miss writes -1 and zeros.
+ *   nerfart_mesh_interp, one thread per pixel: out [n, C] fp32 = fma(w2, a2, fma(w1, a1, w0 * a0)) with a_k the attribute of corner k of the
+ *     pixel's face: attr [V, C] gathered through faces [F, 3] (per vertex), or attr [F, 3, C] with faces == NULL (per corner, e.g. UVs).
+ *     1 <= C <= 8.  face_id < 0 (or a face / vertex index out of range): every channel = fill.
+ *   nerfart_mesh_sample_bilinear, one thread per sample: uv [n, 2] fp32 in PIXEL units of image [Ht, Wt, 3] uint8 under the atlas_uvs /
+ *     write_obj convention (the centre of texel (x, y) is at (x + 0.5, y + 0.5), y runs down).  fp32, every operation rounded once:
+ *     X = u - 0.5, x0 = floor(X) (clamped to [-1, Wt]), tx = X - x0 (clamped to [0, 1]); likewise Y, y0, ty; texel columns x0 and x0 + 1 and
+ *     rows y0 and y0 + 1 clamped into the image (clamp to edge); per channel top = fma(tx, t10 - t00, t00), bot = fma(tx, t11 - t01, t01),
+ *     out = fma(ty, bot - top, top) / 255.  mask [n] uint8 (may be NULL) == 0, or a non-finite uv: out = background [3] (HOST).
+ * Refused with 2 before any launch: a null pointer (of an array that is not empty), H or W (Ht or Wt) outside 1 .. 16384, fx or fy zero, a
+ * non-finite camera number, near not positive and finite, V or F >= 2^31, C outside 1 .. 8. */
+int nerfart_mesh_project(const float* verts, unsigned V, const float* w2c, const float* K5, float near, int* xy_fix, float* cam,
+                         unsigned char* valid, void* stream);
+int nerfart_mesh_raster(const int* xy_fix, const float* cam, const unsigned char* valid, const int* faces, unsigned V, unsigned F, const float* K5,
+                        float near, int H, int W, unsigned long long* zbuf, int* list, int* info, void* stream);
+int nerfart_mesh_resolve(const unsigned long long* zbuf, const float* cam, const int* faces, unsigned V, unsigned F, const float* K5, const float* rot,
+                         int H, int W, int* face_id, float* bary, float* z, float* depth, unsigned char* mask, float* normals, void* stream);
+int nerfart_mesh_interp(const int* face_id, const float* bary, const int* faces, const float* attr, unsigned V, unsigned F, int C, unsigned n,
+                        float fill, float* out, void* stream);
+int nerfart_mesh_sample_bilinear(const float* uv, const unsigned char* mask, const unsigned char* image, int Ht, int Wt, unsigned n,
+                                 const float* background, float* out, void* stream);
+
 /* ---- narrow-band SDF sweep (csrc/mesh_band.hip; mesh_util.banded_volume, extract_mesh(narrow_band=True)): the device side of a sweep that
  * queries the SDF only in the bricks of the grid that can hold the isosurface.  Additions to ABI 5; no counterpart in the reference.  The SDF
  * queries themselves are the caller's: these entry points make points, keep per-brick flags and move values.

@@ -151,6 +151,11 @@ _SIGS = {
     "nerfart_mesh_atlas_layout": (_i, [_ll, _ll, _p]),
     "nerfart_mesh_atlas_points": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p]),
     "nerfart_mesh_project_step": (_i, [_p, _p, _p, _i, _f, _f, _p]),
+    "nerfart_mesh_project": (_i, [_p, _i, _p, _p, _f, _p, _p, _p, _p]),
+    "nerfart_mesh_raster": (_i, [_p, _p, _p, _p, _i, _i, _p, _f, _i, _i, _p, _p, _p, _p]),
+    "nerfart_mesh_resolve": (_i, [_p, _p, _p, _i, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "nerfart_mesh_interp": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _f, _p, _p]),
+    "nerfart_mesh_sample_bilinear": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p]),
     "nerfart_band_workspace_bytes": (_ll, [_i, _i]),
     "nerfart_band_probe_points": (_i, [_i, _i, _d, _d, _p, _p]),
     "nerfart_band_select": (_i, [_i, _p, _f, _f, _i, _i, _p, _p, _p, _p, _p, _ll, _p, _p]),
@@ -558,6 +563,115 @@ def mesh_project_step(points, sdf, nabla, level: float, max_step: float):
                               f"{tuple(nabla.shape)})")
     _check(lib.nerfart_mesh_project_step(_dev(points, name="points"), _dev(sdf, name="sdf"), _dev(nabla, name="nabla"), n, float(level), float(max_step),
                                          _stream()), "nerfart_mesh_project_step")
+
+
+def mesh_camera(c2w, intrinsics):
+    """The HOST numbers the mesh_raster entry points take, from c2w [4, 4] (row-major, OpenCV) and intrinsics [4, 4] (tensors or arrays, read on
+    the host): (w2c [12], rot [9], K5 [5]) as ctypes float arrays.  w2c is the float64 inverse of the fp32 c2w, rounded to fp32 once; rot is c2w's
+    rotation; K5 = (fx, sk, cx, fy, cy) = K[0], K[1], K[2], K[5], K[6] as k_get_rays reads them."""
+    import numpy as np
+    host = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    c = host(c2w).astype(np.float32).reshape(4, 4)
+    k = host(intrinsics).astype(np.float32).reshape(-1)
+    if k.size < 7:
+        raise NerfartHipError(f"intrinsics must hold a 4x4 (or 3x3 padded to it) row-major matrix (got {k.size} numbers)")
+    w2c = np.linalg.inv(c.astype(np.float64))[:3].astype(np.float32).reshape(-1)
+    rot = np.ascontiguousarray(c[:3, :3]).reshape(-1)
+    k5 = np.array([k[0], k[1], k[2], k[5], k[6]], dtype=np.float32)
+    return tuple((C.c_float * len(a))(*[float(x) for x in a]) for a in (w2c, rot, k5))
+
+
+def mesh_project(verts, camera, near: float):
+    """nerfart_mesh_project on verts [V, 3] float32 with camera = mesh_camera(c2w, K): (xy_fix [V, 2] int32 - the pixel position in 1/256 pixel -,
+    cam [V, 3] float32 - the camera-space point -, valid [V] uint8), on verts' device.  No host synchronisation."""
+    if verts.dim() != 2 or verts.shape[1] != 3:
+        raise NerfartHipError(f"verts must be [V, 3] (got {tuple(verts.shape)})")
+    V = int(verts.shape[0])
+    vp = _dev(verts, name="verts")
+    xy_fix = torch.empty(V, 2, dtype=torch.int32, device=verts.device)
+    cam = torch.empty(V, 3, dtype=torch.float32, device=verts.device)
+    valid = torch.empty(V, dtype=torch.uint8, device=verts.device)
+    w2c, _, k5 = camera
+    _check(lib.nerfart_mesh_project(vp, V, C.cast(w2c, C.c_void_p), C.cast(k5, C.c_void_p), float(near), xy_fix.data_ptr(), cam.data_ptr(),
+                                    valid.data_ptr(), _stream()), "nerfart_mesh_project")
+    return xy_fix, cam, valid
+
+
+def mesh_raster(xy_fix, cam, valid, faces, camera, near: float, H: int, W: int):
+    """nerfart_mesh_raster: (zbuf [H * W] int64 holding the uint64 keys (depth bits << 32 | face; all ones = no face), info [4] int32 = (1 if a
+    face holds an index outside [0, V), faces skipped for an invalid vertex, samples rejected by the depth rule, faces that went through the
+    large-face launch)), on faces' device.  No host synchronisation."""
+    V = int(xy_fix.shape[0])
+    if tuple(xy_fix.shape) != (V, 2) or tuple(cam.shape) != (V, 3) or tuple(valid.shape) != (V,):
+        raise NerfartHipError(f"mesh_raster: xy_fix [{V}, 2], cam [{V}, 3], valid [{V}] expected (got {tuple(xy_fix.shape)}, {tuple(cam.shape)}, "
+                              f"{tuple(valid.shape)})")
+    fp, F = _mesh_faces(faces, V)
+    H, W = int(H), int(W)
+    if not (1 <= H <= 16384 and 1 <= W <= 16384):
+        raise NerfartHipError(f"mesh_raster: H and W must be in 1 .. 16384 (got {H}, {W})")
+    zbuf = torch.empty(H * W, dtype=torch.int64, device=faces.device)
+    work = torch.empty(max(F, 1), dtype=torch.int32, device=faces.device)
+    info = torch.empty(4, dtype=torch.int32, device=faces.device)
+    _check(lib.nerfart_mesh_raster(_dev(xy_fix, torch.int32, "xy_fix"), _dev(cam, name="cam"), _dev(valid, torch.uint8, "valid"), fp, V, F,
+                                   C.cast(camera[2], C.c_void_p), float(near), H, W, zbuf.data_ptr(), work.data_ptr(), info.data_ptr(), _stream()),
+           "nerfart_mesh_raster")
+    return zbuf, info
+
+
+def mesh_resolve(zbuf, cam, faces, camera, H: int, W: int):
+    """nerfart_mesh_resolve on mesh_raster's zbuf: dict of face_id [H * W] int32 (-1: no face), bary [H * W, 3], z [H * W] (camera z), depth [H * W]
+    (distance along the unit ray), mask [H * W] uint8, face_normals [H * W, 3] (world space, toward the camera); a miss is 0 in all of them."""
+    V = int(cam.shape[0])
+    fp, F = _mesh_faces(faces, V)
+    H, W = int(H), int(W)
+    if tuple(zbuf.shape) != (H * W,) or tuple(cam.shape) != (V, 3):
+        raise NerfartHipError(f"mesh_resolve: zbuf [{H * W}] and cam [{V}, 3] expected (got {tuple(zbuf.shape)}, {tuple(cam.shape)})")
+    dev, n = zbuf.device, H * W
+    out = {"face_id": torch.empty(n, dtype=torch.int32, device=dev), "bary": torch.empty(n, 3, dtype=torch.float32, device=dev),
+           "z": torch.empty(n, dtype=torch.float32, device=dev), "depth": torch.empty(n, dtype=torch.float32, device=dev),
+           "mask": torch.empty(n, dtype=torch.uint8, device=dev), "face_normals": torch.empty(n, 3, dtype=torch.float32, device=dev)}
+    _check(lib.nerfart_mesh_resolve(_dev(zbuf, torch.int64, "zbuf"), _dev(cam, name="cam"), fp, V, F, C.cast(camera[2], C.c_void_p),
+                                    C.cast(camera[1], C.c_void_p), H, W, *(out[k].data_ptr() for k in ("face_id", "bary", "z", "depth", "mask",
+                                                                                                  "face_normals")), _stream()),
+           "nerfart_mesh_resolve")
+    return out
+
+
+def mesh_interp(face_id, bary, attr, faces=None, fill: float = 0.0):
+    """nerfart_mesh_interp: out [n, C] float32 = sum_k bary[p, k] * (attribute of corner k of face face_id[p]); attr is [V, C] with faces [F, 3] (per
+    vertex, gathered through faces) or [F, 3, C] with faces=None (per corner).  C <= 8; a miss (face_id < 0) gets `fill`."""
+    n = int(face_id.shape[0])
+    if tuple(face_id.shape) != (n,) or tuple(bary.shape) != (n, 3):
+        raise NerfartHipError(f"mesh_interp: face_id [{n}] and bary [{n}, 3] expected (got {tuple(face_id.shape)}, {tuple(bary.shape)})")
+    if faces is not None:
+        if attr.dim() != 2:
+            raise NerfartHipError(f"mesh_interp: per-vertex attributes must be [V, C] (got {tuple(attr.shape)})")
+        V, Cn = int(attr.shape[0]), int(attr.shape[1])
+        fp, F = _mesh_faces(faces, V)
+    else:
+        if attr.dim() != 3 or attr.shape[1] != 3:
+            raise NerfartHipError(f"mesh_interp: per-corner attributes must be [F, 3, C] (got {tuple(attr.shape)})")
+        V, F, Cn, fp = 0, int(attr.shape[0]), int(attr.shape[2]), None
+    if not 1 <= Cn <= 8:
+        raise NerfartHipError(f"mesh_interp: C must be in 1 .. 8 (got {Cn})")
+    out = torch.empty(n, Cn, dtype=torch.float32, device=face_id.device)
+    _check(lib.nerfart_mesh_interp(_dev(face_id, torch.int32, "face_id"), _dev(bary, name="bary"), fp, _dev(attr, name="attr"), V, F, Cn, n, float(fill),
+                                   out.data_ptr(), _stream()), "nerfart_mesh_interp")
+    return out
+
+
+def mesh_sample_bilinear(uv, image, mask=None, background=(0.0, 0.0, 0.0)):
+    """nerfart_mesh_sample_bilinear: rgb [n, 3] float32 = the bilinear sample (clamp to edge, level / 255) of image [Ht, Wt, 3] uint8 at uv [n, 2]
+    float32 in PIXEL units (texel centres at + 0.5, y down: the atlas_uvs convention); mask [n] uint8 == 0, or a non-finite uv, gives `background`."""
+    n = int(uv.shape[0])
+    if tuple(uv.shape) != (n, 2) or image.dim() != 3 or image.shape[2] != 3 or (mask is not None and tuple(mask.shape) != (n,)):
+        raise NerfartHipError(f"mesh_sample_bilinear: uv [{n}, 2], image [Ht, Wt, 3], mask [{n}] expected (got {tuple(uv.shape)}, {tuple(image.shape)}, "
+                              f"{None if mask is None else tuple(mask.shape)})")
+    bg = (C.c_float * 3)(*[float(b) for b in background])
+    out = torch.empty(n, 3, dtype=torch.float32, device=uv.device)
+    _check(lib.nerfart_mesh_sample_bilinear(_dev(uv, name="uv"), _dev(mask, torch.uint8, "mask"), _dev(image, torch.uint8, "image"), int(image.shape[0]),
+                                            int(image.shape[1]), n, C.cast(bg, C.c_void_p), out.data_ptr(), _stream()), "nerfart_mesh_sample_bilinear")
+    return out
 
 
 def band_bricks(N: int, B: int) -> int:

@@ -27,6 +27,9 @@ cells into one, placed by the quadric error metric of the block's faces (csrc/me
 `extract_mesh(texture_model=, filepath="*.obj")` writes a textured mesh - OBJ, MTL, PNG (`write_obj`) - instead of the PLY: `bake_texture` gives
 every face of the final mesh a patch of a per-face atlas and colours every texel at its own point, `texel_points` says where that is
 (csrc/mesh_texture.hip).
+`rasterize` / `render_mesh` look at the mesh that came out, through a rend_util.get_rays camera (csrc/mesh_raster.hip): exact
+integer coverage, a depth test by integer atomics, per-pixel face / barycentrics / depth / normal, then per-vertex colours or the baked texture.
+`read_ply` / `read_obj` read back the files `write_ply` / `write_obj` write.  None of it is on the render or train path.
 """
 import numpy as np
 import torch
@@ -454,6 +457,178 @@ def write_ply(path, verts, faces, normals=None, colors=None):
         out.write(v.tobytes())
         out.write(rec.tobytes())
     return path
+
+
+def read_ply(path):
+    """Reads back exactly the files write_ply writes, and nothing more general: dict of verts [V, 3] float32, faces [F, 3] int32, normals [V, 3]
+    float32 or None, colors [V, 3] uint8 or None (numpy).  ValueError for any other header."""
+    with open(path, "rb") as src:
+        data = src.read()
+    end = data.find(b"end_header\n")
+    if end < 0:
+        raise ValueError(f"read_ply: {path!r} has no PLY header")
+    lines = data[:end].decode("ascii").split("\n")
+    body = data[end + len(b"end_header\n"):]
+    xyz, nrm, rgb = ["property float x", "property float y", "property float z"], ["property float nx", "property float ny", "property float nz"], \
+        ["property uchar red", "property uchar green", "property uchar blue"]
+    if lines[:2] != ["ply", "format binary_little_endian 1.0"] or len(lines) < 8 or not lines[2].startswith("element vertex "):
+        raise ValueError(f"read_ply: {path!r} is not a file write_ply wrote")
+    props = lines[3:-3]
+    fields = [("p", "<f4", (3,))]
+    rest = props[3:]
+    if props[:3] != xyz:
+        raise ValueError(f"read_ply: {path!r} is not a file write_ply wrote (vertex properties {props})")
+    if rest[:3] == nrm:
+        fields.append(("n", "<f4", (3,)))
+        rest = rest[3:]
+    if rest[:3] == rgb:
+        fields.append(("c", "u1", (3,)))
+        rest = rest[3:]
+    if rest or not lines[-3].startswith("element face ") or lines[-2] != "property list uchar int vertex_indices" or lines[-1] != "":
+        raise ValueError(f"read_ply: {path!r} is not a file write_ply wrote (header {lines})")
+    V, F = int(lines[2].split()[2]), int(lines[-3].split()[2])
+    vdt, fdt = np.dtype(fields), np.dtype([("n", "u1"), ("i", "<i4", (3,))])
+    if len(body) != V * vdt.itemsize + F * fdt.itemsize:
+        raise ValueError(f"read_ply: {path!r} holds {len(body)} bytes of data, its header asks for {V * vdt.itemsize + F * fdt.itemsize}")
+    v = np.frombuffer(body, dtype=vdt, count=V)
+    f = np.frombuffer(body, dtype=fdt, count=F, offset=V * vdt.itemsize)
+    if F and not np.all(f["n"] == 3):
+        raise ValueError(f"read_ply: {path!r} holds a face that is not a triangle")
+    names = vdt.names
+    return {"verts": np.array(v["p"], dtype=np.float32), "faces": np.array(f["i"], dtype=np.int32),
+            "normals": np.array(v["n"], dtype=np.float32) if "n" in names else None, "colors": np.array(v["c"], dtype=np.uint8) if "c" in names else None}
+
+
+UV_SNAP = 1024               # read_obj rounds pixel UVs to 1 / UV_SNAP of a texel
+
+
+def read_obj(path):
+    """Reads back exactly the files write_obj writes, and nothing more general: dict of verts [V, 3] float32, faces [F, 3] int32, uv [F, 3, 2]
+    float64 in PIXEL units of image (the v flip undone: X = u W, Y = (1 - v) H), image [H, W, 3] uint8 (the MTL's map_Kd, next to the OBJ, read
+    with PIL), normals [V, 3] float32 or None (numpy).  %.9g gives every fp32 of v and vn back; u and v were printed with nine digits too, which
+    leaves X and Y off by up to 16384 * 5e-10 texels, so they are rounded to the nearest 1 / UV_SNAP of a texel: atlas_uvs (multiples of 1 / 2)
+    come back exactly.  ValueError for any other line."""
+    import os
+    from PIL import Image
+    path = str(path)
+    v, vt, vn, f, mtllib = [], [], [], [], None
+    for line in open(path):
+        tok = line.split()
+        if not tok:
+            continue
+        if tok[0] == "mtllib":
+            mtllib = tok[1]
+        elif tok[0] == "usemtl":
+            pass
+        elif tok[0] in ("v", "vt", "vn"):
+            {"v": v, "vt": vt, "vn": vn}[tok[0]].append([float(t) for t in tok[1:]])
+        elif tok[0] == "f" and len(tok) == 4:
+            f.append([[int(i) for i in t.split("/")] for t in tok[1:]])
+        else:
+            raise ValueError(f"read_obj: unexpected line {line!r}")
+    if mtllib is None:
+        raise ValueError(f"read_obj: {path!r} names no material library")
+    folder = os.path.dirname(path)
+    png = None
+    for line in open(os.path.join(folder, mtllib)):
+        tok = line.split()
+        if tok and tok[0] == "map_Kd":
+            png = tok[1]
+    if png is None:
+        raise ValueError(f"read_obj: {mtllib!r} names no texture (map_Kd)")
+    image = np.array(Image.open(os.path.join(folder, png)).convert("RGB"), dtype=np.uint8)
+    H, W = image.shape[:2]
+    f = np.array(f, dtype=np.int64).reshape(len(f), 3, -1)
+    F = len(f)
+    vt = np.array(vt, dtype=np.float64).reshape(-1, 2)
+    if f.shape[2] not in (2, 3) or len(vt) != 3 * F or not np.array_equal(f[..., 1], np.arange(3 * F).reshape(F, 3) + 1) or \
+            (f.shape[2] == 3 and not np.array_equal(f[..., 2], f[..., 0])):
+        raise ValueError(f"read_obj: {path!r} is not a file write_obj wrote (one vt per face corner, in order; vn indexed as v)")
+    pix = np.stack([vt[:, 0] * W, (1.0 - vt[:, 1]) * H], axis=-1)
+    uv = (np.round(pix * UV_SNAP) / UV_SNAP).reshape(F, 3, 2)
+    return {"verts": np.array(v, dtype=np.float64).reshape(-1, 3).astype(np.float32), "faces": (f[..., 0] - 1).astype(np.int32), "uv": uv, "image": image,
+            "normals": np.array(vn, dtype=np.float64).reshape(-1, 3).astype(np.float32) if vn else None}
+
+
+RASTER_MAX_SIDE = 16384      # the largest image side of the rasteriser (csrc/mesh_raster.hip MAX_SIDE)
+
+
+def _gpu_mesh(verts, faces, who):
+    if not (torch.is_tensor(verts) and torch.is_tensor(faces) and verts.is_cuda and faces.is_cuda):
+        raise ValueError(f"{who}: verts and faces must be tensors on the GPU (there is no CPU path)")
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"{who}: verts must be [V, 3] and faces [F, 3] (got {tuple(verts.shape)}, {tuple(faces.shape)})")
+
+
+@torch.no_grad()
+def rasterize(verts, faces, c2w, intrinsics, H: int, W: int, near: float = 1e-3):
+    """The mesh (verts [V, 3] float32, faces [F, 3] int32, on the GPU) seen by the camera (c2w [4, 4], intrinsics [4, 4]: rend_util.get_rays'
+    conventions - pixel (column i, row j) sampled at its integer coordinates, ray index j W + i) - csrc/mesh_raster.hip, the rules are in
+    include/nerfart_hip.h.  dict, every array over the H W pixels: face_id int32 (-1: nothing hit), bary [., 3], depth (distance along the unit
+    ray: the units of render_fn's depth_volume and surface_render's depths), z (camera z), mask uint8, face_normals [., 3] (world space,
+    geometric, turned toward the camera); n_skipped (int: faces dropped whole because a vertex is behind `near` or projects beyond 2^15 pixels -
+    there is no polygon clipping) and n_rejected (int: covered samples whose plane depth is not >= near).  Coverage is exact (integer edge
+    functions on positions snapped to 1/256 pixel, top-left rule): faces sharing an edge neither overlap nor leave a gap, and the image does not
+    depend on the order of the faces or of the work.  One host read (the counts and the flag); a face index outside [0, V) raises ValueError."""
+    from . import hip
+    _gpu_mesh(verts, faces, "rasterize")
+    H, W = int(H), int(W)
+    if not (1 <= H <= RASTER_MAX_SIDE and 1 <= W <= RASTER_MAX_SIDE):
+        raise ValueError(f"rasterize: H and W must be in 1 .. {RASTER_MAX_SIDE} (got {H}, {W})")
+    if not (float(near) > 0.0 and np.isfinite(near)):
+        raise ValueError(f"rasterize: near must be positive and finite (got {near})")
+    camera = hip.mesh_camera(c2w, intrinsics)
+    xy_fix, cam, valid = hip.mesh_project(verts, camera, near)
+    zbuf, info = hip.mesh_raster(xy_fix, cam, valid, faces, camera, near, H, W)
+    out = hip.mesh_resolve(zbuf, cam, faces, camera, H, W)
+    bad, n_skipped, n_rejected, _ = (int(c) for c in info.cpu())
+    if bad:
+        raise ValueError(f"rasterize: a face holds a vertex index outside [0, {int(verts.shape[0])})")
+    out["n_skipped"], out["n_rejected"] = n_skipped, n_rejected
+    return out
+
+
+@torch.no_grad()
+def render_mesh(verts, faces, c2w, intrinsics, H: int, W: int, colors=None, uv=None, image=None, normals=None, background=(0, 0, 0), near: float = 1e-3):
+    """A frame of the mesh, in render_fn's triple shape: (rgb [H W, 3] float32, depth [H W] float32, extras).  rasterize(...) decides what every
+    pixel sees; then the pixel is shaded from exactly one of: colors [V, 3] per vertex (uint8 levels, taken / 255, or float) interpolated over
+    the face; uv [F, 3, 2] (pixel units, atlas_uvs' convention) with image [Ht, Wt, 3] uint8 - what bake_texture returns and read_obj reads -,
+    the interpolated uv sampled bilinearly; neither: the face normal as a colour, (n + 1) / 2.  A pixel that sees nothing gets `background` and
+    depth 0.  extras: mask_mesh [H W] bool, normals_mesh [H W, 3] (normals [V, 3] interpolated and renormalised when given, otherwise the face
+    normal; 0 on a miss), face_id, bary, n_skipped."""
+    from . import hip
+    if (uv is None) != (image is None):
+        raise ValueError("render_mesh: uv and image go together")
+    if colors is not None and uv is not None:
+        raise ValueError("render_mesh: give colors or uv + image, not both")
+    r = rasterize(verts, faces, c2w, intrinsics, H, W, near)
+    dev = verts.device
+    bg = [float(b) for b in background]
+    face_id, bary, mask = r["face_id"], r["bary"], r["mask"]
+    if normals is not None:
+        n_mesh = hip.normalize_dirs(hip.mesh_interp(face_id, bary, torch.as_tensor(normals, device=dev).float().contiguous(), faces))
+    else:
+        n_mesh = r["face_normals"]
+    if uv is not None:
+        uv_t = torch.as_tensor(np.asarray(uv, dtype=np.float32) if not torch.is_tensor(uv) else uv, device=dev).float().contiguous()
+        img = torch.as_tensor(image, device=dev).contiguous()
+        if tuple(uv_t.shape) != (int(faces.shape[0]), 3, 2) or img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
+            raise ValueError(f"render_mesh: uv must be [{int(faces.shape[0])}, 3, 2] and image uint8 [Ht, Wt, 3] (got {tuple(uv_t.shape)}, {img.dtype} "
+                             f"{tuple(img.shape)})")
+        rgb = hip.mesh_sample_bilinear(hip.mesh_interp(face_id, bary, uv_t), img, mask, bg)
+    else:
+        if colors is not None:
+            col = torch.as_tensor(colors, device=dev)
+            col = (col.float() / 255.0 if col.dtype == torch.uint8 else col.float()).contiguous()
+            if tuple(col.shape) != (int(verts.shape[0]), 3):
+                raise ValueError(f"render_mesh: colors must be [{int(verts.shape[0])}, 3] (got {tuple(col.shape)})")
+            rgb = hip.mesh_interp(face_id, bary, col, faces)
+        else:
+            rgb = 0.5 * n_mesh + 0.5
+        hit = mask.bool()[:, None]
+        rgb = torch.where(hit, rgb, torch.tensor(bg, dtype=torch.float32, device=dev))
+    extras = {"mask_mesh": mask.bool(), "normals_mesh": n_mesh, "face_id": face_id, "bary": bary, "n_skipped": r["n_skipped"]}
+    return rgb, r["depth"], extras
 
 
 @torch.no_grad()

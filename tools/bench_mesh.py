@@ -8,7 +8,11 @@ the dense sweep's mesh bit for bit.  `--simplify C` adds the simplify stage on t
 halves (nerfart_mesh_simplify_count, _emit) and V, F -> V', F'.  `--texture P [--texture_project K]` adds the texture bake of that mesh (the
 simplified one with --simplify, else marching cubes' own) in the model's frame: nerfart_mesh_atlas_points, the K projection steps (SDF + gradient
 queries and nerfart_mesh_project_step; the step kernel also alone), the colour queries, mesh_util.bake_texture as a whole, and - once, on the
-host's clock - mesh_util.write_obj.  DESIGN.md 4.7 says which of these figures have been taken."""
+host's clock - mesh_util.write_obj.  `--render H W` adds the rasteriser (csrc/mesh_raster.hip) on that mesh (the simplified one with --simplify) in
+the model's frame, seen by scene.camera(H, W): the three raster stages each alone (nerfart_mesh_project, _raster, _resolve), mesh_util.rasterize as
+a whole (with its one host read), and the shading calls - nerfart_mesh_interp of per-corner UVs and nerfart_mesh_sample_bilinear on an atlas of
+patch --texture (default 4) filled with noise: the sampling cost does not depend on what the texels hold.  DESIGN.md 4.7 says which of these
+figures have been taken."""
 import argparse, json, os, statistics, sys, tempfile, time
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -38,6 +42,7 @@ def main():
     ap.add_argument("--simplify", type=int, default=None, help="also time mesh_util.simplify_clusters with this cluster factor on the extracted mesh")
     ap.add_argument("--texture", type=int, default=None, help="also time the texture bake (mesh_util.bake_texture) with this patch size")
     ap.add_argument("--texture_project", type=int, default=2, help="projection steps of --texture")
+    ap.add_argument("--render", type=int, nargs=2, default=None, metavar=("H", "W"), help="also time the rasteriser on the extracted mesh at this image size")
     args = ap.parse_args()
     from nerfart_amd import scene, mesh_util, hip
     dev = torch.device("cuda", 0)
@@ -119,6 +124,33 @@ def main():
             res["texture_png_MiB"] = round(os.path.getsize(os.path.join(tmp, "bench.png")) / 2 ** 20, 2)
         res.update(texture_patch=P, texture_project=K, texture_faces=int(tfaces.shape[0]), texture_image=[W, H], texture_valid_texels=int(start.shape[0]),
                    texture_points_bytes=W * H * 16 + int(tfaces.shape[0]) * 12)      # written per texel: 12 + 4; the faces read once (vertices from cache)
+    if args.render:                                                # the rasteriser on the final mesh, in the model's frame
+        H, W = args.render
+        if args.simplify:
+            rverts, rfaces = mesh_util.grid_to_frame(out_v, *mesh_util.model_frame(N, vs)), out_f
+        else:
+            rverts, rfaces = hip.mc_emit(vol, 0.0, *mesh_util.model_frame(N, vs), ws, V, F)
+        c2w, K = scene.camera(H, W)
+        camera, near = hip.mesh_camera(c2w, K), 1e-3
+        xy_fix, cam, valid = hip.mesh_project(rverts, camera, near)                            # warm-ups
+        zbuf, info = hip.mesh_raster(xy_fix, cam, valid, rfaces, camera, near, H, W)
+        r = hip.mesh_resolve(zbuf, cam, rfaces, camera, H, W)
+        res["render_project_ms"], _ = timed(lambda: hip.mesh_project(rverts, camera, near), args.iters)
+        res["render_raster_ms"], _ = timed(lambda: hip.mesh_raster(xy_fix, cam, valid, rfaces, camera, near, H, W), args.iters)
+        res["render_resolve_ms"], _ = timed(lambda: hip.mesh_resolve(zbuf, cam, rfaces, camera, H, W), args.iters)
+        res["render_rasterize_ms"], _ = timed(lambda: mesh_util.rasterize(rverts, rfaces, c2w, K, H, W, near), args.iters)
+        P = args.texture or 4
+        _, _, _, Wt, Ht = hip.mesh_atlas_layout(rfaces.shape[0], P)
+        uv = torch.from_numpy(mesh_util.atlas_uvs(rfaces.shape[0], P)).float().to(dev).contiguous()
+        atlas = torch.randint(0, 256, (Ht, Wt, 3), dtype=torch.uint8, device=dev)
+        pix_uv = hip.mesh_interp(r["face_id"], r["bary"], uv)
+        hip.mesh_sample_bilinear(pix_uv, atlas, r["mask"])
+        res["render_interp_uv_ms"], _ = timed(lambda: hip.mesh_interp(r["face_id"], r["bary"], uv), args.iters)
+        res["render_sample_bilinear_ms"], _ = timed(lambda: hip.mesh_sample_bilinear(pix_uv, atlas, r["mask"]), args.iters)
+        bad, n_skipped, n_rejected, n_large = (int(c) for c in info.cpu())
+        assert not bad
+        res.update(render_image=[W, H], render_vertices=int(rverts.shape[0]), render_faces=int(rfaces.shape[0]), render_covered_pixels=int(r["mask"].sum()),
+                   render_n_skipped=n_skipped, render_n_rejected=n_rejected, render_large_faces=n_large, render_atlas=[Wt, Ht])
     print(json.dumps(res))
 
 
