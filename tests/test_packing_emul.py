@@ -11,8 +11,17 @@ import emul_chain as em
 from nerfart_amd import packing
 
 
-def _blobs(fw):
-    sd, _ = scene_state(fw, 0.01 if fw == "VolSDF" else None)
+def _sd(fw, state="scene"):
+    """'scene': the seeded scene_state(); 'trained': tests/point_query_ref.py's trained-like state (dense encoding columns, non-zero hidden and
+    feature biases, weight_g far from |weight_v|) - the bit-level model walks the real blob, so this holds packing.py's bias and aux layout."""
+    if state == "trained":
+        import point_query_ref
+        return point_query_ref.trained_like_state(fw, 0)
+    return scene_state(fw, 0.01 if fw == "VolSDF" else None)[0]
+
+
+def _blobs(fw, state="scene"):
+    sd = _sd(fw, state)
     surf = packing.surface_plan().pack(packing.surface_tensors(sd)).numpy()
     vt = 1 if fw == "VolSDF" else 3
     rad = packing.radiance_plan(vt).pack(packing.radiance_tensors(sd)).numpy()
@@ -39,8 +48,8 @@ def test_blob_header_and_chunk_table():
     assert _blobs("NeuS")[2][:512].view(np.int32)[2] == 42
 
 
-def test_emulated_sdf_only_matches_oracle():
-    sd, surf, _, _ = _blobs("VolSDF")
+def test_emulated_sdf_only_matches_oracle(state="scene"):
+    sd, surf, _, _ = _blobs("VolSDF", state)
     g = torch.Generator().manual_seed(7)
     pts = (torch.rand(16, 3, generator=g) * 6 - 3)
     pts[:4] *= 0.3
@@ -51,8 +60,8 @@ def test_emulated_sdf_only_matches_oracle():
     np.testing.assert_allclose(em.emul_sdf_only(surf, pts.numpy(), 0.0), ref_nc, atol=3e-6, rtol=1e-5)
 
 
-def test_emulated_sdf_nabla_matches_oracle():
-    sd, surf, _, _ = _blobs("VolSDF")
+def test_emulated_sdf_nabla_matches_oracle(state="scene"):
+    sd, surf, _, _ = _blobs("VolSDF", state)
     g = torch.Generator().manual_seed(8)
     pts = (torch.rand(4, 3, generator=g) * 4 - 2)
     sdf, nab, h7 = em.emul_sdf_nabla(surf, pts.numpy(), 3.0)
@@ -67,10 +76,10 @@ def test_emulated_sdf_nabla_matches_oracle():
     np.testing.assert_allclose(h7 @ w8[1:].T + b8[1:], feat_ref.numpy(), atol=1e-5, rtol=1e-4)
 
 
-def test_emulated_reverse_mode_sdf_grad_matches_oracle():
+def test_emulated_reverse_mode_sdf_grad_matches_oracle(state="scene"):
     """k_sdf_grad's data flow (forward sweep keeping softplus', transposed chunks, 3-tile encoding tails, Jacobian of the encoding)
     on the packed blob, against autograd on the oracle's SDF net."""
-    sd, surf, _, _ = _blobs("VolSDF")
+    sd, surf, _, _ = _blobs("VolSDF", state)
     g = torch.Generator().manual_seed(12)
     pts = (torch.rand(16, 3, generator=g) * 4 - 2)
     pts[:3] *= 0.2
@@ -86,8 +95,8 @@ def test_emulated_reverse_mode_sdf_grad_matches_oracle():
 
 
 @pytest.mark.parametrize("fw", ["VolSDF", "NeuS"])
-def test_emulated_radiance_matches_oracle(fw):
-    sd, surf, rad, vt = _blobs(fw)
+def test_emulated_radiance_matches_oracle(fw, state="scene"):
+    sd, surf, rad, vt = _blobs(fw, state)
     g = torch.Generator().manual_seed(9)
     pts = (torch.rand(16, 3, generator=g) * 2 - 1)
     view = torch.nn.functional.normalize(torch.randn(16, 3, generator=g), dim=-1)
@@ -100,8 +109,8 @@ def test_emulated_radiance_matches_oracle(fw):
 
 
 # ---- split-bf16 ("bf16x3") programs ---------------------------------------------------------------------
-def _blobs_bf16(fw):
-    sd, _ = scene_state(fw, 0.01 if fw == "VolSDF" else None)
+def _blobs_bf16(fw, state="scene"):
+    sd = _sd(fw, state)
     surf = packing.surface_plan_bf16().pack(packing.surface_tensors(sd)).numpy()
     vt = 1 if fw == "VolSDF" else 3
     rad = packing.radiance_plan_bf16(vt).pack(packing.radiance_tensors(sd)).numpy()
@@ -119,8 +128,8 @@ def test_bf16_blob_header():
         assert offs[-2] + 16384 <= blob.size          # the stream copies 64 KiB per chunk
 
 
-def test_emulated_bf16_sdf_only_matches_oracle():
-    sd, surf, _, _ = _blobs_bf16("VolSDF")
+def test_emulated_bf16_sdf_only_matches_oracle(state="scene"):
+    sd, surf, _, _ = _blobs_bf16("VolSDF", state)
     g = torch.Generator().manual_seed(17)
     pts = (torch.rand(32, 3, generator=g) * 6 - 3)
     pts[:8] *= 0.3
@@ -129,8 +138,8 @@ def test_emulated_bf16_sdf_only_matches_oracle():
     np.testing.assert_allclose(out, ref, atol=1e-4, rtol=1e-4)
 
 
-def test_emulated_bf16_sdf_nabla_matches_oracle():
-    sd, surf, _, _ = _blobs_bf16("VolSDF")
+def test_emulated_bf16_sdf_nabla_matches_oracle(state="scene"):
+    sd, surf, _, _ = _blobs_bf16("VolSDF", state)
     g = torch.Generator().manual_seed(18)
     pts = (torch.rand(8, 3, generator=g) * 4 - 2)
     parts = [em.emul_sdf_nabla_bf16(surf, pts[i:i + 4].numpy(), 3.0) for i in (0, 4)]
@@ -146,8 +155,8 @@ def test_emulated_bf16_sdf_nabla_matches_oracle():
 
 
 @pytest.mark.parametrize("fw", ["VolSDF", "NeuS"])
-def test_emulated_bf16_radiance_matches_oracle(fw):
-    sd, surf, rad, vt = _blobs_bf16(fw)
+def test_emulated_bf16_radiance_matches_oracle(fw, state="scene"):
+    sd, surf, rad, vt = _blobs_bf16(fw, state)
     g = torch.Generator().manual_seed(19)
     pts = (torch.rand(32, 3, generator=g) * 2 - 1)
     view = torch.nn.functional.normalize(torch.randn(32, 3, generator=g), dim=-1)
@@ -159,9 +168,9 @@ def test_emulated_bf16_radiance_matches_oracle(fw):
     np.testing.assert_allclose(out, ref, atol=2e-4, rtol=1e-3)
 
 
-def test_emulated_bf16_reverse_mode_grad_matches_oracle():
+def test_emulated_bf16_reverse_mode_grad_matches_oracle(state="scene"):
     """Forward program + transposed-weight backward program of the surface blob (k_sdf_grad_bf16's data flow)."""
-    sd, surf, _, _ = _blobs_bf16("VolSDF")
+    sd, surf, _, _ = _blobs_bf16("VolSDF", state)
     hdr = surf[:512].view(np.int32)
     assert hdr[2] == 30 and hdr[6] == 59
     g = torch.Generator().manual_seed(23)
@@ -179,9 +188,9 @@ def test_emulated_bf16_reverse_mode_grad_matches_oracle():
 
 
 @pytest.mark.parametrize("fw", ["VolSDF", "NeuS"])
-def test_emulated_bf16_radiance_backward_matches_autograd(fw):
+def test_emulated_bf16_radiance_backward_matches_autograd(fw, state="scene"):
     """Transposed-weight program of the radiance blob (k_radiance_bwd_bf16's data flow) against torch autograd."""
-    sd, surf, rad, vt = _blobs_bf16(fw)
+    sd, surf, rad, vt = _blobs_bf16(fw, state)
     hdr = rad[:512].view(np.int32)
     assert hdr[2] == 21 and hdr[6] == 42
     g = torch.Generator().manual_seed(29)
@@ -238,10 +247,10 @@ def _w32_C_to_regs(C):
     return out
 
 
-def test_w32_program_register_path_matches_oracle():
+def test_w32_program_register_path_matches_oracle(state="scene"):
     """Walks the fourth program of the split-bf16 surface blob exactly as mlp_k2_w32.hip does - fragments -> 32x32x16 MFMAs ->
     C registers -> (softplus) -> the next layer's B units straight from the registers - for one wave (32 columns)."""
-    sd, _ = scene_state("VolSDF", 0.01)
+    sd = _sd("VolSDF", state)
     plan = packing.surface_plan_bf16()
     blob = plan.pack(packing.surface_tensors(sd))
     hdr = blob[:512].view(torch.int32).numpy()
@@ -310,11 +319,11 @@ def test_w32_program_register_path_matches_oracle():
 
 
 # ---- the 2-MFMA variant (C-ABI precision 4, csrc/mlp_chain_f16x2.hip): fp16 hi + lo weight fragments, one fp16 activation term ------------
-def test_emulated_fp16x2_kernels_walk_the_fp16_blob():
+def test_emulated_fp16x2_kernels_walk_the_fp16_blob(state="scene"):
     """The same programs packed with term="fp16" (fp16 fragments; the reverse chunks without the folded 1 / 65535) through the same
     emulated data flow with single-term fp16 activations: sdf / nabla / h7 / rgb land within the 11-bit-activation error of the
     oracle - a wrong fragment decode, a missing scale or an fp16 underflow of the transposed weights would miss by orders of magnitude."""
-    sd, _ = scene_state("VolSDF", 0.01)
+    sd = _sd("VolSDF", state)
     surf = packing.surface_plan_bf16(term="fp16").pack(packing.surface_tensors(sd)).numpy()
     rad = packing.radiance_plan_bf16(1, term="fp16").pack(packing.radiance_tensors(sd)).numpy()
     g = torch.Generator().manual_seed(23)
@@ -343,3 +352,21 @@ def test_emulated_fp16x2_kernels_walk_the_fp16_blob():
     ref = nets.radiance_forward(sd, pts, view, n_ref, feat_ref, -1, -1).numpy()
     np.testing.assert_allclose(rgb, ref, atol=1e-2)
     assert err_s > 1e-6, "suspiciously exact: is the emulation really on the fp16 path?"
+
+
+# ---- the same emulation-against-oracle tests on the trained-like state ----------------------------------------------------------------------------
+@pytest.mark.parametrize("test", [test_emulated_sdf_only_matches_oracle, test_emulated_sdf_nabla_matches_oracle, test_emulated_reverse_mode_sdf_grad_matches_oracle,
+                                  test_emulated_bf16_sdf_only_matches_oracle, test_emulated_bf16_sdf_nabla_matches_oracle,
+                                  test_emulated_bf16_reverse_mode_grad_matches_oracle, test_w32_program_register_path_matches_oracle,
+                                  test_emulated_fp16x2_kernels_walk_the_fp16_blob], ids=lambda f: f.__name__[5:])
+def test_on_the_trained_like_state(test):
+    """Every hidden bias of scene_state() is 0 and its encoding columns are noise: a bias register, an aux section or an encoding column in the wrong
+    place changes nothing there.  The same walks of the real blob, with the same assertions, on the state where each of them moves the result."""
+    test(state="trained")
+
+
+@pytest.mark.parametrize("fw", ["VolSDF", "NeuS"])
+@pytest.mark.parametrize("test", [test_emulated_radiance_matches_oracle, test_emulated_bf16_radiance_matches_oracle,
+                                  test_emulated_bf16_radiance_backward_matches_autograd], ids=lambda f: f.__name__[5:])
+def test_radiance_on_the_trained_like_state(test, fw):
+    test(fw, state="trained")
