@@ -769,6 +769,7 @@ int nerfart_wgrad_bf16(const void* Z, long long z_stride, const void* A, long lo
  *     else 0; R_bg <= 0: no sphere, NeuS), nbar[R P,3] = g_n + the eikonal term's gradient w 2 (|n| - 1) n / (|n| N) with N = the points of the ray's reference
  *     patch (eik_group_rays rays per patch inside this launch, the last one ragged; <= 0: one patch), eik_ray[R] = each ray's share
  *     of w * mean_patch((|n| - 1)^2) (their sum = the sum of the patches' eikonal losses).  w_eikonal = 0: no eikonal term.
+ *     A sample with n = 0 gets no eikonal gradient (the zero subgradient of |n|, as torch's norm backward) and still counts (0 - 1)^2 in eik_ray.
  *   nerfart_wgrad_operand_*: the narrow (a_cols = 64) operands of nerfart_wgrad_bf16 from fp32 data: hi parts bf16(x) in columns
  *     0..c-1 and, when c <= 32, lo parts bf16(x - hi) in columns 32..32+c-1 (add the two halves of dW); rows M.. zero.
  *       _embed_pair: [2 rows_pad, 64]: embed(pts) (models/base.py:46-64, multires < 0: identity) in rows 0.., its tangent along dir in

@@ -153,15 +153,16 @@ def _eikonal_terms(nab, R: int, P: int, w_eikonal: float, group_rays):
     ragged).  group_rays None: one patch.  (The torch statement of what nerfart_volsdf_pass2_cotangents computes: tests.)"""
     nn_ = nab.norm(dim=-1)
     err = nn_ - 1.0
+    unit = torch.where(nn_ > 0, err / nn_, torch.zeros_like(nn_))      # n = 0: the zero subgradient of |n|, as torch's norm backward (not -inf * 0)
     if group_rays is None or group_rays >= R:
-        return w_eikonal * (err ** 2).mean(), (w_eikonal * 2.0 / nn_.numel()) * (err / nn_)[:, None] * nab
+        return w_eikonal * (err ** 2).mean(), (w_eikonal * 2.0 / nn_.numel()) * unit[:, None] * nab
     wr = torch.full((R,), 1.0 / (group_rays * P), device=nab.device)
     tail = R % group_rays
     if tail:
         wr[R - tail:] = 1.0 / (tail * P)
     eik = w_eikonal * ((err ** 2).reshape(R, P).sum(1) * wr).sum()
     coef = (2.0 * w_eikonal) * wr[:, None].expand(R, P).reshape(-1)
-    return eik, (coef * err / nn_)[:, None] * nab
+    return eik, (coef * unit)[:, None] * nab
 
 
 def _native_backward(model, who: str, device, accum, call):

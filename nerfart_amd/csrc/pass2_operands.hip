@@ -113,7 +113,7 @@ k_volsdf_cotangents(const float* __restrict__ pts, const float* __restrict__ sdf
             const float nn = sqrtf(nx * nx + ny * ny + nz * nz);
             const float err = nn - 1.0f;
             acc = fmaf(err, err, acc);
-            const float k = (2.0f * w_eik) * coef * err / nn;
+            const float k = nn != 0.f ? (2.0f * w_eik) * coef * err / nn : 0.f;   // n = 0: the zero subgradient of |n| (torch's norm backward), not -inf * 0
             bx = fmaf(k, nx, bx); by = fmaf(k, ny, by); bz = fmaf(k, nz, bz);
         }
         if (g_n_extra) { bx += g_n_extra[3 * m]; by += g_n_extra[3 * m + 1]; bz += g_n_extra[3 * m + 2]; }
