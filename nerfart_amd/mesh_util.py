@@ -15,22 +15,23 @@ table-based marching cubes on the case table nerfart_amd/mc_table.py generates -
 triangulation inside ambiguous cells differs ("deviations").  `backend="skimage"` keeps the reference's route through
 scikit-image and plyfile, for machines that have them.
 
-Beyond the reference, off by default: `extract_mesh(refine_evals=, vertex_normals=, color_model=)` keeps every vertex as (grid edge, t) and moves t
-against the SDF without leaving the edge (`refine_vertices`; csrc/mesh_vertices.hip), and writes per-vertex normals (the SDF gradient) and
-colours (the radiance net looking down the normal; `vertex_attributes`) as extra PLY vertex properties.
-`extract_mesh(keep_largest=, min_component_faces=)` drops the floaters: `mesh_components` labels the connected components of the indexed mesh
-on the GPU (csrc/mesh_components.hip), `filter_components` keeps the largest ones and compacts vertices and faces.
-`extract_mesh(narrow_band=True)` replaces the N^3 sweep by `banded_volume`: the SDF is queried only in the bricks of the grid that can hold the
-level set, the rest is filled with a value of the right sign, and the result checks and repairs itself (csrc/mesh_band.hip).
-`extract_mesh(simplify_factor=c)` decimates the mesh before it is written: `simplify_clusters` merges the vertices of every block of c^3 grid
-cells into one, placed by the quadric error metric of the block's faces (csrc/mesh_simplify.hip).
-`extract_mesh(texture_model=, filepath="*.obj")` writes a textured mesh - OBJ, MTL, PNG (`write_obj`) - instead of the PLY: `bake_texture` gives
-every face of the final mesh a patch of a per-face atlas and colours every texel at its own point, `texel_points` says where that is
-(csrc/mesh_texture.hip).
+Beyond the reference, each off by default, the native route of `extract_mesh` is one sequence of public stage functions (its docstring: the order,
+the options, the refusals; DESIGN.md 4.7: the kernels).  Sweep: narrow_band=True makes it `banded_volume` - the SDF is queried only in the bricks
+of the grid that can hold the level set, the rest is filled with a value of the right sign, and the result checks and repairs itself
+(csrc/mesh_band.hip).  Vertices: refine_evals= / vertex_normals= / color_model= / simplify_factor= / texture_model= keep every vertex as (grid edge, t),
+and `refine_vertices` moves t against the SDF without leaving the edge (csrc/mesh_vertices.hip).  simplify_factor=c: `simplify_clusters` merges the
+vertices of every block of c^3 grid cells into one, placed by the quadric error metric of the block's faces (csrc/mesh_simplify.hip).  Per-vertex
+normals (the SDF gradient) and colours (the radiance net looking down the normal; `vertex_attributes`) become extra PLY vertex properties.
+keep_largest= / min_component_faces= drop the floaters: `mesh_components` labels the connected components of the indexed mesh on the GPU
+(csrc/mesh_components.hip), `filter_components` keeps the largest ones and compacts vertices and faces.  texture_model= with filepath="*.obj" writes
+a textured mesh - OBJ, MTL, PNG (`write_obj`) - instead of the PLY: `bake_texture` gives every face of the final mesh a patch of a per-face atlas
+and colours every texel at its own point, `texel_points` says where that is (csrc/mesh_texture.hip).
 `rasterize` / `render_mesh` look at the mesh that came out, through a rend_util.get_rays camera (csrc/mesh_raster.hip): exact
 integer coverage, a depth test by integer atomics, per-pixel face / barycentrics / depth / normal, then per-vertex colours or the baked texture.
 `read_ply` / `read_obj` read back the files `write_ply` / `write_obj` write.  None of it is on the render or train path.
 """
+import types
+
 import numpy as np
 import torch
 
@@ -152,12 +153,18 @@ def marching_cubes(vol, level: float = 0.0, spacing=(1.0, 1.0, 1.0), origin=(0.0
     (v1 - v0) x (v2 - v0) points to the outside (outward for a signed distance).  Vertex and face order are defined (points resp. cells in linear
     order), so two calls give identical tensors.  One host read (the two sizes and the non-finite flag) sits between counting and emitting;
     a non-finite value raises ValueError; no crossing gives (0, 3) tensors.  CPU tensors are refused: there is no CPU path."""
+    return _count_and_emit(vol, level, origin, spacing)[:2]
+
+
+def _count_and_emit(vol, level, origin, spacing):
+    """marching_cubes keeping what hip.mc_emit_edges and refine_vertices read to give its V vertices as (grid edge, t): (verts, faces, ws, V)."""
     from . import hip                                              # here, not at import: grid_points and write_ply need no library
     ws, counts = hip.mc_count(vol, level)
     V, F, bad = (int(c) for c in counts.cpu())
     if bad:
         raise ValueError("marching_cubes: the volume holds non-finite values")
-    return hip.mc_emit(vol, level, origin, spacing, ws, V, F)
+    verts, faces = hip.mc_emit(vol, level, origin, spacing, ws, V, F)
+    return verts, faces, ws, V
 
 
 def model_frame(N: int, volume_size: float):
@@ -631,157 +638,43 @@ def render_mesh(verts, faces, c2w, intrinsics, H: int, W: int, colors=None, uv=N
     return rgb, r["depth"], extras
 
 
-@torch.no_grad()
-def _extract_mesh_with_vertex_data(implicit_surface, volume_size, level, N, filepath, chunk, refine_evals, vertex_normals, color_model,
-                                   keep_largest=None, min_component_faces=None, narrow_band=False, band_brick=8, band_lipschitz=BAND_LIPSCHITZ,
-                                   band_info=None, simplify_factor=None, simplify_reg=0.01, texture_model=None, texture_patch=4, texture_project=0):
-    """extract_mesh with any of refine_evals / vertex_normals / color_model / simplify_factor / texture_model set: every vertex is (edge, t); positions are written
-    in the placement frame, every network query is made in the model's frame, so the refinement does not depend on how the mesh is placed.
-    Without simplify_factor components are dropped once, at the end, from positions, faces, normals and colours together.  With it the
-    (refined) vertices are taken in grid coordinates, floaters go first - before clustering can weld them to the surface -, simplify_clusters
-    merges the rest, and normals and colours are queried at the NEW vertices only.  With texture_model the bake comes last, on the final mesh in
-    the model's frame (bake_texture), and the mesh is written as OBJ + MTL + PNG instead of PLY."""
-    from . import hip
-
-    def write(verts, faces, normals, colors, model_pts):
-        """The file: PLY, or with texture_model the textured OBJ - model_pts() gives the final vertices in the model's frame."""
-        if texture_model is None:
-            return write_ply(filepath, verts, faces, normals, colors)
-        image, uv = bake_texture(model_pts(), faces, lambda p: normal_view_radiance(texture_model, p)[1], patch=texture_patch,
-                                 query_fn=implicit_surface.forward_with_nablas, project=texture_project, level=level,
-                                 max_step=(simplify_factor or 1) * volume_size / N)
-        return write_obj(filepath, verts, faces, uv, image, normals)
-
-    if refine_evals < 0:
-        raise ValueError(f"extract_mesh: refine_evals must be >= 0 (got {refine_evals})")
-    vol = (sdf_volume(implicit_surface, volume_size, N, chunk, narrow_band=True, band_brick=band_brick, band_lipschitz=band_lipschitz, level=level,
-                      band_info=band_info) if narrow_band else sdf_volume(implicit_surface, volume_size, N, chunk))
-    ws, counts = hip.mc_count(vol, level)
-    V, F, bad = (int(c) for c in counts.cpu())
-    if bad:
-        raise ValueError("marching_cubes: the volume holds non-finite values")
-    place_o, place_s = placement_frame(N, volume_size)
-    verts, faces = hip.mc_emit(vol, level, place_o, place_s, ws, V, F)
-    if refine_evals >= 1:
-        edge, t, _ = refine_vertices(implicit_surface, vol, level, ws, V, volume_size, refine_evals)
-        verts = hip.mesh_edge_points(edge, t, vol.shape, place_o, place_s)
-    else:
-        edge, _, t, _, _ = hip.mc_emit_edges(vol, level, ws, V)
-    normals = colors = None
-    if simplify_factor is not None:
-        grid = hip.mesh_edge_points(edge, t, vol.shape, [0.0] * 3, [1.0] * 3)
-        if keep_largest is not None or min_component_faces is not None:
-            grid, faces, _ = filter_components(grid, faces, keep_largest, min_component_faces)
-        grid, faces, _ = simplify_clusters(grid, faces, vol.shape, simplify_factor, simplify_reg)
-        verts = grid_to_frame(grid, place_o, place_s)
-        if vertex_normals or color_model is not None:
-            pts = grid_to_frame(grid, *model_frame(N, volume_size))
-            if color_model is not None:
-                normals, colors = vertex_attributes(color_model, pts)
-            else:
-                normals = hip.normalize_dirs(implicit_surface.forward_with_nablas(pts)[1].contiguous()) if pts.shape[0] else pts
-        return write(verts, faces, normals if vertex_normals else None, colors, lambda: grid_to_frame(grid, *model_frame(N, volume_size)))
-    if vertex_normals or color_model is not None:
-        pts = hip.mesh_edge_points(edge, t, vol.shape, *model_frame(N, volume_size))
-        if color_model is not None:
-            normals, colors = vertex_attributes(color_model, pts)
-        else:
-            normals = hip.normalize_dirs(implicit_surface.forward_with_nablas(pts)[1].contiguous()) if V else pts
-    src = None
-    if keep_largest is not None or min_component_faces is not None:
-        verts, faces, src = filter_components(verts, faces, keep_largest, min_component_faces)
-        normals, colors = (a if a is None else a[src.long()] for a in (normals, colors))
-
-    def model_pts():
-        pts = hip.mesh_edge_points(edge, t, vol.shape, *model_frame(N, volume_size))
-        return pts if src is None else pts[src.long()]
-    return write(verts, faces, normals if vertex_normals else None, colors, model_pts)
-
-
-def extract_mesh(implicit_surface, volume_size=2.0, level=0.0, N=512, filepath="./surface.ply", show_progress=True, chunk=1 << 24,
-                 reference_shear: bool = False, backend: str = "native", refine_evals: int = 0, vertex_normals: bool = False, color_model=None,
-                 keep_largest: int = None, min_component_faces: int = None, narrow_band: bool = False, band_brick: int = 8,
-                 band_lipschitz: float = BAND_LIPSCHITZ, band_info: dict = None, simplify_factor: int = None, simplify_reg: float = 0.01,
-                 texture_model=None, texture_patch: int = 4, texture_project: int = 0):
-    """mesh_util.extract_mesh: SDF volume -> marching cubes -> .ply.  backend="native" (default): marching_cubes + write_ply above, nothing
-    third-party, the volume stays on the GPU; backend="skimage": the reference's route (needs scikit-image and plyfile).  Both place the mesh as
-    the reference does: spacing volume_size / N, offset -volume_size / 2 (mesh_util.py:112).  reference_shear=True samples
-    the sheared grid the reference's true-division index arithmetic produces under Python 3 (vertex-for-vertex parity with its
-    meshes); the default is the regular grid ("deviations").  show_progress is accepted for call compatibility:
-    the sweep is a handful of kernel launches, there is nothing to show.
-
-    Three options without a reference counterpart (native backend, regular grid; all at their defaults: the path above, untouched):
-    refine_evals >= 1 moves every vertex along its grid edge to the best of that many SDF evaluations (refine_vertices; 1 = the interpolated
-    vertex), vertex_normals writes nx ny nz = the normalised SDF gradient, color_model (the whole VolSDF / NeuS model) writes red green blue =
-    its radiance looking down the normal (vertex_attributes).  Faces are marching_cubes' own, unchanged.
-
-    keep_largest / min_component_faces (native backend, the sheared grid included; both None: the paths above, untouched) drop the floaters
-    before the file is written: only the keep_largest largest connected components, and / or only those of at least min_component_faces faces,
-    survive (filter_components; csrc/mesh_components.hip), with their vertices, normals and colours.
-
-    narrow_band=True (native backend, regular grid; False: the paths above, untouched) sweeps the SDF only in the bricks of band_brick^3 grid
-    points that can hold the level set, given |grad sdf| <= band_lipschitz (banded_volume; csrc/mesh_band.hip): the file is the dense sweep's byte
-    for byte when the bound holds.  A piece of surface lying wholly inside bricks the bound wrongly ruled out is not found; a dict passed as
-    band_info receives the sweep's counts.  ValueError with reference_shear=True (not the lattice the bound is stated on) and with
-    backend="skimage" (Lewiner's ambiguity tests read corner values that would be fill values).
-
-    simplify_factor=c >= 2 (native backend, regular grid; None: the paths above, untouched) merges the vertices of every block of c^3 grid cells
-    into one, placed by the quadrics of the block's faces (simplify_clusters; csrc/mesh_simplify.hip; simplify_reg pulls it toward the members'
-    mean): roughly c^2 times fewer triangles.  The order is marching cubes, refinement, keep_largest / min_component_faces, clustering, and only
-    then vertex_normals / color_model, queried at the new vertices.  ValueError with reference_shear=True (the clusters are blocks of the regular
-    lattice) and with backend="skimage" (the clustering runs on the GPU, on the native extractor's vertices).
-
-    texture_model (the whole VolSDF / NeuS model; native backend, regular grid; None: the paths above, untouched) writes a textured mesh instead
-    of a PLY: filepath must end in .obj, and <stem>.obj, <stem>.mtl and <stem>.png are written (write_obj); the .obj path is returned.  The bake
-    runs last - marching cubes, refinement, keep_largest / min_component_faces, clustering, then bake_texture on the final mesh in the model's
-    frame: every face owns a patch of texture_patch texel intervals along its legs in a per-face atlas, every texel is vertex_attributes'
-    colour rule (the radiance looking down the normal) at the texel's own point.  texture_project = k moves the texels k Newton steps onto the
-    level set first, each at most (simplify_factor or 1) * volume_size / N long - a decimated face is a chord of the surface.  vertex_normals
-    become the OBJ's vn.  ValueError: a path not ending in .obj, color_model as well (OBJ has no standard vertex colours), reference_shear=True,
-    backend="skimage", a mesh without faces or one whose atlas would pass 16384 texels a side (use simplify_factor or a smaller patch)."""
-    if texture_model is not None:
-        if not str(filepath).endswith(".obj"):
-            raise ValueError(f"extract_mesh: texture_model writes OBJ + MTL + PNG: filepath must end in .obj (got {filepath!r})")
-        if color_model is not None:
+def _check_extract_options(o):
+    """Every refusal of extract_mesh for its arguments o (+ o.edges: stage 3 is wanted); the first rule broken names the ValueError: the order is behaviour."""
+    if o.texture_model is not None:
+        if not str(o.filepath).endswith(".obj"):
+            raise ValueError(f"extract_mesh: texture_model writes OBJ + MTL + PNG: filepath must end in .obj (got {o.filepath!r})")
+        if o.color_model is not None:
             raise ValueError("extract_mesh: texture_model and color_model exclude each other (OBJ has no standard vertex colours)")
-        if reference_shear:
+        if o.reference_shear:
             raise ValueError("extract_mesh: texture_model needs the regular grid (reference_shear=True samples a sheared lattice, which has no "
                              "regular frame to query the model in)")
-        if backend == "skimage":
+        if o.backend == "skimage":
             raise ValueError("extract_mesh: texture_model needs backend='native' (the atlas is baked on the GPU, on the native extractor's mesh)")
-        if int(texture_patch) < 1 or int(texture_project) < 0:
-            raise ValueError(f"extract_mesh: texture_patch must be >= 1 and texture_project >= 0 (got {texture_patch}, {texture_project})")
-    if simplify_factor is not None and reference_shear:
+        if int(o.texture_patch) < 1 or int(o.texture_project) < 0:
+            raise ValueError(f"extract_mesh: texture_patch must be >= 1 and texture_project >= 0 (got {o.texture_patch}, {o.texture_project})")
+    if o.simplify_factor is not None and o.reference_shear:
         raise ValueError("extract_mesh: simplify_factor needs the regular grid (reference_shear=True samples a sheared lattice, whose cells are not "
                          "the blocks the clusters are made of)")
-    if simplify_factor is not None and backend == "skimage":
+    if o.simplify_factor is not None and o.backend == "skimage":
         raise ValueError("extract_mesh: simplify_factor needs backend='native' (the clustering runs on the GPU, on the native extractor's vertices)")
-    if narrow_band and reference_shear:
+    if o.narrow_band and o.reference_shear:
         raise ValueError("extract_mesh: narrow_band needs the regular grid (reference_shear=True samples a sheared lattice, on which the bound of "
                          "the band test is not stated)")
-    if narrow_band and backend == "skimage":
-        raise ValueError("extract_mesh: narrow_band needs backend='native' (scikit-image's Lewiner variant reads corner values that would be fill "
-                         "values)")
-    filtering = keep_largest is not None or min_component_faces is not None
-    if filtering and backend != "native":
+    if o.narrow_band and o.backend == "skimage":
+        raise ValueError("extract_mesh: narrow_band needs backend='native' (scikit-image's Lewiner variant reads corner values that would be fill values)")
+    if (o.keep_largest is not None or o.min_component_faces is not None) and o.backend != "native":
         raise ValueError("extract_mesh: keep_largest / min_component_faces need backend='native' (the components are found on the GPU)")
-    if refine_evals or vertex_normals or color_model is not None or simplify_factor is not None or texture_model is not None:
-        if reference_shear or backend != "native":
-            raise ValueError("extract_mesh: refine_evals / vertex_normals / color_model need backend='native' and the regular grid "
-                             "(the sheared grid has no regular frame, scikit-image gives no edge table)")
-        return _extract_mesh_with_vertex_data(implicit_surface, volume_size, level, N, filepath, chunk, int(refine_evals), vertex_normals, color_model,
-                                              keep_largest, min_component_faces, narrow_band, band_brick, band_lipschitz, band_info,
-                                              simplify_factor, simplify_reg, texture_model, int(texture_patch), int(texture_project))
-    if backend == "native":
-        vol = (sdf_volume(implicit_surface, volume_size, N, chunk, narrow_band=True, band_brick=band_brick, band_lipschitz=band_lipschitz,
-                          level=level, band_info=band_info) if narrow_band
-               else sdf_volume(implicit_surface, volume_size, N, chunk, reference_shear=reference_shear))
-        verts, faces = marching_cubes(vol, level=level, spacing=[volume_size / N] * 3, origin=[-volume_size / 2.0] * 3)
-        if filtering:
-            verts, faces, _ = filter_components(verts, faces, keep_largest, min_component_faces)
-        return write_ply(filepath, verts, faces)
-    if backend != "skimage":
-        raise ValueError(f"extract_mesh: backend must be 'native' or 'skimage' (got {backend!r})")
+    if o.edges and (o.reference_shear or o.backend != "native"):
+        raise ValueError("extract_mesh: refine_evals / vertex_normals / color_model need backend='native' and the regular grid "
+                         "(the sheared grid has no regular frame, scikit-image gives no edge table)")
+    if o.backend not in ("native", "skimage"):
+        raise ValueError(f"extract_mesh: backend must be 'native' or 'skimage' (got {o.backend!r})")
+    if int(o.refine_evals) < 0:
+        raise ValueError(f"extract_mesh: refine_evals must be >= 0 (got {int(o.refine_evals)})")
+
+
+def _extract_skimage(implicit_surface, volume_size, level, N, filepath, chunk, reference_shear):
+    """The reference's route: the volume on the host, scikit-image's marching cubes, plyfile's two elements."""
     try:
         from skimage import measure
         import plyfile
@@ -795,3 +688,110 @@ def extract_mesh(implicit_surface, volume_size=2.0, level=0.0, N=512, filepath="
     f = np.array([(list(t),) for t in faces], dtype=[("vertex_indices", "i4", (3,))])
     plyfile.PlyData([plyfile.PlyElement.describe(v, "vertex"), plyfile.PlyElement.describe(f, "face")]).write(filepath)
     return filepath
+
+
+class _Mesh:
+    """The mesh between the stages of the native pipeline: verts [V, 3] in the placement frame - what is written -, faces [F, 3] int32, optional
+    normals and colors [V, 3], and place(origin, spacing) -> the vertices [V0, 3] in any other frame, from their edge records or their grid
+    coordinates (None on the plain path, which keeps neither); src: the rows of place's result that stage 6 left (None: all of them)."""
+    def __init__(self, verts, faces, place=None):
+        self.verts, self.faces, self.place, self.normals, self.colors, self.src = verts, faces, place, None, None, None
+
+    def points(self, origin, spacing):
+        pts = self.place(origin, spacing)
+        return pts if self.src is None else pts[self.src.long()]
+
+
+def _normals_and_colors(implicit_surface, color_model, pts):
+    """(normals, colors) at the model-frame pts [V, 3]: vertex_attributes, or with no color_model the normalised SDF gradient and None; V = 0: no query."""
+    from . import hip
+    if pts.shape[0] == 0:
+        return pts, (None if color_model is None else torch.zeros(0, 3, dtype=torch.uint8, device=pts.device))
+    if color_model is not None:
+        return vertex_attributes(color_model, pts)
+    return hip.normalize_dirs(implicit_surface.forward_with_nablas(pts)[1].contiguous()), None
+
+
+@torch.no_grad()
+def _extract_native(implicit_surface, o):
+    """extract_mesh(backend="native") after validation, o its arguments: the stages of extract_mesh's docstring, in its order."""
+    from . import hip
+    N, volume_size, level, filtering = o.N, o.volume_size, o.level, o.keep_largest is not None or o.min_component_faces is not None
+    placement, model = placement_frame(N, volume_size), model_frame(N, volume_size)
+    vol = sdf_volume(implicit_surface, volume_size, N, o.chunk, o.reference_shear, o.narrow_band, o.band_brick, o.band_lipschitz, level, o.band_info)
+    verts, faces, ws, V = _count_and_emit(vol, level, *placement)
+    mesh = _Mesh(verts, faces)
+    if o.edges:
+        if int(o.refine_evals) >= 1:
+            edge, t, _ = refine_vertices(implicit_surface, vol, level, ws, V, volume_size, int(o.refine_evals))
+        else:
+            edge, _, t, _, _ = hip.mc_emit_edges(vol, level, ws, V)
+        mesh.place = lambda origin, spacing: hip.mesh_edge_points(edge, t, vol.shape, origin, spacing)
+        if int(o.refine_evals) >= 1:
+            mesh.verts = mesh.place(*placement)
+    if o.simplify_factor is not None:
+        grid = mesh.place([0.0] * 3, [1.0] * 3)
+        if filtering:                                               # before clustering can weld a floater to the surface
+            grid, faces, _ = filter_components(grid, faces, o.keep_largest, o.min_component_faces)
+        grid, faces, _ = simplify_clusters(grid, faces, vol.shape, o.simplify_factor, o.simplify_reg)
+        mesh = _Mesh(grid_to_frame(grid, *placement), faces, lambda origin, spacing: grid_to_frame(grid, origin, spacing))
+    if o.vertex_normals or o.color_model is not None:
+        mesh.normals, mesh.colors = _normals_and_colors(implicit_surface, o.color_model, mesh.points(*model))
+    if filtering and o.simplify_factor is None:
+        mesh.verts, mesh.faces, mesh.src = filter_components(mesh.verts, mesh.faces, o.keep_largest, o.min_component_faces)
+        mesh.normals, mesh.colors = (a if a is None else a[mesh.src.long()] for a in (mesh.normals, mesh.colors))
+    normals = mesh.normals if o.vertex_normals else None
+    if o.texture_model is None:
+        return write_ply(o.filepath, mesh.verts, mesh.faces, normals, mesh.colors)
+    image, uv = bake_texture(mesh.points(*model), mesh.faces, lambda p: normal_view_radiance(o.texture_model, p)[1], patch=int(o.texture_patch),
+                             query_fn=implicit_surface.forward_with_nablas, project=int(o.texture_project), level=level,
+                             max_step=(o.simplify_factor or 1) * volume_size / N)
+    return write_obj(o.filepath, mesh.verts, mesh.faces, uv, image, normals)
+
+
+def extract_mesh(implicit_surface, volume_size=2.0, level=0.0, N=512, filepath="./surface.ply", show_progress=True, chunk=1 << 24,
+                 reference_shear: bool = False, backend: str = "native", refine_evals: int = 0, vertex_normals: bool = False, color_model=None,
+                 keep_largest: int = None, min_component_faces: int = None, narrow_band: bool = False, band_brick: int = 8,
+                 band_lipschitz: float = BAND_LIPSCHITZ, band_info: dict = None, simplify_factor: int = None, simplify_reg: float = 0.01,
+                 texture_model=None, texture_patch: int = 4, texture_project: int = 0):
+    """mesh_util.extract_mesh: SDF volume -> marching cubes -> a mesh file; returns filepath.  At the defaults: the reference's call and its
+    two-element PLY.  Two frames: the mesh is PLACED as the reference places it, spacing volume_size / N, offset -volume_size / 2 (mesh_util.py:112;
+    placement_frame); every network query of a vertex or texel is made in the MODEL's frame, the swept grid's, spacing volume_size / (N - 1)
+    (model_frame), so no query depends on the placement.  show_progress is accepted for call compatibility: the sweep is a handful of kernel
+    launches, there is nothing to show.  The arguments are checked first (last paragraph): a refused call imports, queries and writes nothing.
+
+    backend="skimage": the reference's route (needs scikit-image and plyfile) - the volume goes to the host, Lewiner's marching cubes, plyfile;
+    of the options it takes reference_shear alone.  backend="native" (default; nothing third-party, the volume stays on the GPU) is one
+    sequence, a stage whose options are off being skipped; all off, stages 1, 2 and 7 are marching_cubes + write_ply:
+      1. sdf_volume.  reference_shear=True samples the sheared grid the reference's true-division index arithmetic produces under Python 3
+         (vertex-for-vertex parity with its meshes); the default is the regular grid ("deviations").  narrow_band=True sweeps
+         only the bricks of band_brick^3 grid points that can hold the level set, given |grad sdf| <= band_lipschitz (banded_volume;
+         csrc/mesh_band.hip): the file is the dense sweep's byte for byte when the bound holds; a piece of surface lying wholly inside bricks the
+         bound wrongly ruled out is not found; a dict passed as band_info receives the sweep's counts.
+      2. Marching cubes at `level` (a non-finite volume: ValueError), vertices in the placement frame; faces: these until stage 4 or 6 changes them.
+      3. With any of refine_evals, vertex_normals, color_model, simplify_factor, texture_model: every vertex as (grid edge, t).  refine_evals >= 1
+         moves t to the best of that many SDF evaluations (refine_vertices; 1 = the interpolated vertex) and the positions are emitted anew.
+      4. simplify_factor=c >= 2, on grid coordinates: keep_largest / min_component_faces drop the floaters first - clustering could weld them to
+         the surface -, then the vertices of every block of c^3 grid cells become one, placed by the quadrics of the block's faces
+         (simplify_clusters; csrc/mesh_simplify.hip; simplify_reg pulls it toward the members' mean): roughly c^2 times fewer triangles.
+      5. At the vertices there are now: vertex_normals writes nx ny nz = the normalised SDF gradient, color_model (the whole VolSDF / NeuS model)
+         red green blue = its radiance looking down the normal (vertex_attributes).
+      6. Without simplify_factor, keep_largest / min_component_faces (the sheared grid included): only the keep_largest largest connected components,
+         and / or those of at least min_component_faces faces, survive (filter_components; csrc/mesh_components.hip), with normals and colours.
+      7. write_ply; with texture_model (the whole model) write_obj instead: <stem>.obj, .mtl and .png, the .obj path returned, vertex_normals as
+         the OBJ's vn.  bake_texture runs on the final mesh in the model's frame: every face owns a patch of texture_patch texel intervals along
+         its legs in a per-face atlas, every texel is vertex_attributes' colour rule at the texel's own point; texture_project = k first moves the
+         texels k Newton steps onto the level set, each at most (simplify_factor or 1) * volume_size / N long - a decimated face is a chord of
+         the surface.  A mesh without faces, or an atlas past 16384 texels a side (use simplify_factor or a smaller patch): ValueError.
+
+    Refused, the first that applies: texture_model with a filepath not ending in .obj, with color_model (OBJ has no standard vertex colours), with
+    reference_shear, with backend="skimage", with texture_patch < 1 or texture_project < 0; simplify_factor, then narrow_band, with reference_shear
+    (clusters and bricks are blocks of the regular lattice) or backend="skimage" (the clustering runs on the native extractor's vertices; Lewiner's
+    ambiguity tests would read fill values); keep_largest / min_component_faces off the native backend (the components are found on the GPU);
+    stage 3 with reference_shear or off the native backend (no regular frame; no edge table); an unknown backend; refine_evals < 0."""
+    o = types.SimpleNamespace(**locals())                            # the arguments as one value: the checks and the stages read them by name
+    o.edges = bool(refine_evals or vertex_normals or color_model is not None or simplify_factor is not None or texture_model is not None)   # stage 3
+    _check_extract_options(o)
+    if backend == "skimage":
+        return _extract_skimage(implicit_surface, volume_size, level, N, filepath, chunk, reference_shear)
+    return _extract_native(implicit_surface, o)

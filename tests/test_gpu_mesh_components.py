@@ -9,6 +9,7 @@ import torch
 import mc_ref
 import mesh_components_ref as ref
 import mesh_vertices_ref as mv
+from mesh_pipeline_ref import WithFloaters
 from test_mesh_components_ref import MESHES, mesh
 
 pytestmark = pytest.mark.gpu
@@ -252,28 +253,13 @@ def test_three_spheres_through_marching_cubes():
         assert mc_ref.is_closed(f2) and mc_ref.is_consistently_oriented(f2) and mc_ref.euler_characteristic(len(src), f2) == 2 * spheres
 
 
-class _WithFloaters(torch.nn.Module):
-    """The model's SDF with two small spheres far from the object united to it: the floaters of a fine-tuned field, made on purpose."""
-    SPHERES = (((1.2, 1.2, 1.2), 0.15), ((-1.2, 1.1, -1.2), 0.1))
-
-    def __init__(self, surface):
-        super().__init__()
-        self.surface = surface
-
-    def forward(self, x):
-        d = self.surface.forward(x)
-        for c, r in self.SPHERES:
-            d = torch.minimum(d, (x - torch.tensor(c, device=x.device)).norm(dim=-1) - r)
-        return d
-
-
 @pytest.mark.parametrize("reference_shear", [False, True])
 def test_extract_mesh_drops_the_floaters(reference_shear, tmp_path):
     """The plain native path, sheared grid included: the filtered file is the reference's filter of the unfiltered file, byte for byte."""
     from nerfart_amd import scene, mesh_util
     N, volume_size = 48, 3.0
     model, _, _ = scene.build_model("NeuS", seed=0, beta=None, device=DEV)
-    surface = _WithFloaters(model.implicit_surface)
+    surface = WithFloaters(model.implicit_surface)
     kw = dict(volume_size=volume_size, N=N, reference_shear=reference_shear)
     _, verts, faces, _ = mc_ref.read_ply(mesh_util.extract_mesh(surface, filepath=str(tmp_path / "all.ply"), **kw))
     label, n_faces, info = ref.components(faces, len(verts))

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+import mesh_pipeline_ref
 import mesh_raster_ref as ref
 
 pytestmark = pytest.mark.gpu
@@ -334,13 +335,8 @@ def model(request):
 
 @pytest.fixture(scope="module")
 def decimated(model):
-    """(vertices in the model's frame, in the placement frame, faces) of extract_mesh(simplify_factor=FACTOR), as tests/test_gpu_mesh_texture.py
-    builds them."""
-    from nerfart_amd import mesh_util
-    vol = mesh_util.sdf_volume(model.implicit_surface, VOLUME_SIZE, N)
-    verts, faces = mesh_util.marching_cubes(vol, 0.0)
-    g, f, _ = mesh_util.simplify_clusters(verts, faces, vol.shape, FACTOR)
-    return (mesh_util.grid_to_frame(g, *mesh_util.model_frame(N, VOLUME_SIZE)), mesh_util.grid_to_frame(g, *mesh_util.placement_frame(N, VOLUME_SIZE)), f)
+    """(vertices in the model's frame, in the placement frame, faces) of extract_mesh(simplify_factor=FACTOR), by hand."""
+    return mesh_pipeline_ref.decimated(model.implicit_surface, N, VOLUME_SIZE, FACTOR)
 
 
 def _camera():

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import mesh_texture_ref as ref
+from mesh_pipeline_ref import decimated
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -281,15 +282,6 @@ def model(request):
     return scene.build_model(request.param, seed=0, beta=0.01 if request.param == "VolSDF" else None, device=DEV, precision="mixed")[0]
 
 
-def final_mesh(surface):
-    """(vertices in the model's frame, in the placement frame, faces) of extract_mesh(simplify_factor=FACTOR), by hand."""
-    from nerfart_amd import mesh_util
-    vol = mesh_util.sdf_volume(surface, VOLUME_SIZE, N)
-    verts, faces = mesh_util.marching_cubes(vol, 0.0)
-    g, f, _ = mesh_util.simplify_clusters(verts, faces, vol.shape, FACTOR)
-    return (mesh_util.grid_to_frame(g, *mesh_util.model_frame(N, VOLUME_SIZE)), mesh_util.grid_to_frame(g, *mesh_util.placement_frame(N, VOLUME_SIZE)), f)
-
-
 def test_extract_mesh_writes_the_textured_mesh(model, tmp_path):
     from nerfart_amd import hip, mesh_util
     surface = model.implicit_surface
@@ -297,7 +289,7 @@ def test_extract_mesh_writes_the_textured_mesh(model, tmp_path):
     path = mesh_util.extract_mesh(surface, filepath=str(tmp_path / "mesh.obj"), texture_model=model, texture_patch=PATCH, texture_project=PROJECT, **kw)
     assert path == str(tmp_path / "mesh.obj") and all(os.path.exists(str(tmp_path / ("mesh" + e))) for e in (".obj", ".mtl", ".png"))
     obj, mtl, png = ref.read_obj(path), ref.read_mtl(str(tmp_path / "mesh.mtl")), ref.read_png(str(tmp_path / "mesh.png"))
-    pts, placed, faces = final_mesh(surface)
+    pts, placed, faces = decimated(surface, N, VOLUME_SIZE, FACTOR)              # extract_mesh(simplify_factor=FACTOR) by hand
     V, F = pts.shape[0], faces.shape[0]
     S, Cw, Ch, W, H = ref.layout(F, PATCH)
     assert F > 100 and png.shape == (H, W, 3) and mtl["map_Kd"] == "mesh.png" and obj["mtllib"] == "mesh.mtl"
