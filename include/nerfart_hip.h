@@ -676,6 +676,76 @@ int nerfart_mesh_interp(const int* face_id, const float* bary, const int* faces,
 int nerfart_mesh_sample_bilinear(const float* uv, const unsigned char* mask, const unsigned char* image, int Ht, int Wt, unsigned n,
                                  const float* background, float* out, void* stream);
 
+/* ---- distance between two meshes (csrc/mesh_distance.hip; mesh_util.sample_surface / closest_on_mesh / mesh_distance, tools/compare_mesh.py):
+ * area-weighted samples of one indexed mesh and, for any points, the exact closest point of another.  Additions to ABI 5; no counterpart in the
+ * reference.  verts [V, 3] fp32, faces [F, 3] int32.  tests/mesh_distance_ref.py states all of this in numpy.  All floating point here is fp64 from
+ * the fp32 inputs, every operation rounded once (no fused multiply-add), sums of three as (x + y) + z, in the order written.  No float atomics;
+ * results are a pure function of the inputs: two calls give the same bits.  Everything runs on the caller's stream in the caller's workspace.
+ *   A BAD face has an index outside [0, V) or a non-finite vertex coordinate; every other face is GOOD (a zero-area face is good).
+ *   THE HASHES, in wrapping 32-bit unsigned arithmetic:
+ *       mix(x):  x ^= x >> 16;  x *= 0x7feb352d;  x ^= x >> 15;  x *= 0x846ca68b;  x ^= x >> 16
+ *       key(seed, f) = mix(mix(seed) ^ mix(f + 0x9e3779b9))
+ *       h(seed, f) = mix(key ^ 0x68e31da4) / 2^32                                  - in [0, 1), exact in fp64
+ *       s(seed, f, j) = mix(key + 0x85ebca6b (j + 1));  u = mix(s ^ 0xb5297a4d) / 2^32,  v = mix(s ^ 0x1b56c4e9) / 2^32
+ *   SAMPLING, count: per good face e1 = b - a, e2 = c - a; n = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x);
+ *     a_f = 0.5 sqrt((nx nx + ny ny) + nz nz); x_f = density a_f + h(seed, f); n_f = floor(x_f) samples - stochastic rounding: the expected count
+ *     is density a_f, every face independent of every other.  A bad face gets none; a zero-area face gets none by the rule (h < 1).  x_f >= 2^31:
+ *     none, and the overflow flag.  The offsets are the exclusive scan of n_f (csrc/pair_scan.h, no atomics).
+ *   SAMPLING, emit: sample i belongs to the face f with off[f] <= i < off[f] + n_f, j = i - off[f]; (u, v) from the hash; u + v > 1: u = 1 - u,
+ *     v = 1 - v (reflected into the triangle); point[k] = float((a[k] + u e1[k]) + v e2[k]).  Samples come face by face: spatially coherent.
+ *   nerfart_mesh_sample_workspace_bytes(F): the workspace of the two calls below (0 = refused, see nerfart_last_error).  It BEGINS with
+ *     off [max(F, 1)][2] uint32: off[f][0] = the offset of face f's first sample, off[f][1] = the bad faces before f.
+ *   nerfart_mesh_sample_count: fills the workspace and info [4] uint32 (DEVICE, 8-byte aligned) = {n, bad faces, 1 if a count or their sum
+ *     reached 2^31 (the other outputs then mean nothing), 0}.  Asynchronous.
+ *   nerfart_mesh_sample_emit, after a host read of n, from the SAME untouched workspace and the same mesh and seed: points [n, 3] fp32,
+ *     face [n] int32.  n is the size of the caller's arrays: every write is checked against it, and an element beyond the workspace's own total
+ *     is written as (0, 0, 0), -1.  n == 0 launches nothing.
+ *   THE DISTANCE of a point p to a good face (a, b, c), squared: the minimum of
+ *       the three point-segment terms, for (a, b), (b, c), (c, a): e = end - start, w = p - start, ee = e . e, t = clamp((w . e) / ee, 0, 1)
+ *         (t = 0 when ee == 0), q = w - t e, the term q . q; and,
+ *       when nn = n . n > 0 with n = (b - a) x (c - a), and the three edge functions n . ((b - a) x (p - a)), n . ((c - b) x (p - b)),
+ *         n . ((a - c) x (p - c)) are all >= 0: the plane term (n . (p - a))^2 / nn.
+ *     A degenerate face is thus its edges.  The RESULT for p is the lexicographic minimum of (d^2, face) over all good faces: ties go to the
+ *     lowest face index, and the order in which faces are visited does not matter.
+ *   THE GRID (gx, gy, gz) spans the box [lo, hi] of the good faces' vertices (exact: integer atomicMin / atomicMax on the order-preserving
+ *     encoding of the fp32 bits).  Per axis: cell size s = (hi - lo) / g, inv = g / (hi - lo), the cell of x = clamp(floor((x - lo) inv), 0, g - 1);
+ *     an axis with hi == lo has ONE cell whatever g says, and so has every axis when there is no good face.  The linear index is
+ *     (cx gy + cy) gz + cz.  A good face is entered into every cell its axis-aligned box overlaps (cell of its min .. cell of its max per axis:
+ *     conservative): counted per cell by integer atomicAdd, scanned, then written through per-cell integer cursors.  The order within a cell is
+ *     free because the query takes a minimum.
+ *   THE SEARCH, per point: its own cell c (clamped, so a point outside the box starts at the nearest boundary cell); for r = 0, 1, ... the cells
+ *     of Chebyshev distance exactly r from c that exist; after ring r the visited box is [c - r, c + r] cut to the grid, and nothing unvisited
+ *     is nearer than B = the smallest of p[k] - (lo[k] + (c[k] - r) s[k]) over the axes with c[k] - r > 0 and (lo[k] + (c[k] + r + 1) s[k]) - p[k]
+ *     over those with c[k] + r < g[k] - 1: the inward distances to the sides of the visited box that are not the grid's own boundary (no such
+ *     side: everything has been visited).  B is made conservative against the rounding of the cell rule: B' = max(B (1 - 2^-20) - 2^-30 m, 0),
+ *     m = the largest |coordinate| of the box + the largest of p.  The search STOPS after the ring at which min(best d, max_distance) < B',
+ *     strictly, so that an unvisited face can never tie with the reported one: the answer does not depend on the grid.
+ *   nerfart_mesh_grid_workspace_bytes(gx, gy, gz): the grid's workspace (0 = refused).
+ *   nerfart_mesh_grid_count: box, cell counts and offsets into the workspace; info [2] uint64 (DEVICE, 8-byte aligned) = {entries, good faces}.
+ *     With 2^31 entries or more nothing is counted per cell, and nerfart_mesh_grid_fill / nerfart_mesh_closest refuse such a number.
+ *   nerfart_mesh_grid_fill, after a host read of `entries`, same mesh, grid and workspace: list [entries] int32, the faces cell by cell.
+ *   nerfart_mesh_closest: points [n, 3] fp32 against the mesh through the filled workspace and list (neither is modified).  dist [n] fp32 = the
+ *     fp64 square root of the minimum, rounded once; face [n] int32.  max_distance (double >= 0, infinity allowed) bounds the search: a point
+ *     with d > max_distance reports dist = float(max_distance), face = -1, and so does every point when the mesh has no good face.  A point
+ *     with a non-finite coordinate reports NaN, -1.  visited [n] uint32 (may be NULL) = the faces tested for the point, with repetition.
+ *     One thread per point; every loop is bounded by the grid, the ring and the cell's count; every read of list is checked against entries.
+ * Refused with 2 before any launch: a null pointer (of an array that is not empty), V, F or n >= 2^31, info not 8-byte aligned, a density that
+ * is negative or not finite, n > 0 with F == 0 (emit), a grid dimension outside 1 .. 1024 or more than 2^24 cells, entries >= 2^31,
+ * max_distance negative or NaN, a workspace smaller than the query's answer (or not 16-byte aligned). */
+size_t nerfart_mesh_sample_workspace_bytes(unsigned F);
+int nerfart_mesh_sample_count(const float* verts, const int* faces, unsigned V, unsigned F, double density, unsigned seed, void* ws, size_t ws_bytes,
+                              unsigned* info, void* stream);
+int nerfart_mesh_sample_emit(const float* verts, const int* faces, unsigned V, unsigned F, unsigned seed, const void* ws, size_t ws_bytes, float* points,
+                             int* face, unsigned n, void* stream);
+size_t nerfart_mesh_grid_workspace_bytes(int gx, int gy, int gz);
+int nerfart_mesh_grid_count(const float* verts, const int* faces, unsigned V, unsigned F, int gx, int gy, int gz, void* ws, size_t ws_bytes,
+                            unsigned long long* info, void* stream);
+int nerfart_mesh_grid_fill(const float* verts, const int* faces, unsigned V, unsigned F, int gx, int gy, int gz, void* ws, size_t ws_bytes, int* list,
+                           unsigned long long entries, void* stream);
+int nerfart_mesh_closest(const float* points, unsigned n, const float* verts, const int* faces, unsigned V, unsigned F, int gx, int gy, int gz,
+                         const void* ws, size_t ws_bytes, const int* list, unsigned long long entries, double max_distance, float* dist, int* face,
+                         unsigned* visited, void* stream);
+
 /* ---- narrow-band SDF sweep (csrc/mesh_band.hip; mesh_util.banded_volume, extract_mesh(narrow_band=True)): the device side of a sweep that
  * queries the SDF only in the bricks of the grid that can hold the isosurface.  Additions to ABI 5; no counterpart in the reference.  The SDF
  * queries themselves are the caller's: these entry points make points, keep per-brick flags and move values.

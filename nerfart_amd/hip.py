@@ -156,6 +156,13 @@ _SIGS = {
     "nerfart_mesh_resolve": (_i, [_p, _p, _p, _i, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
     "nerfart_mesh_interp": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _f, _p, _p]),
     "nerfart_mesh_sample_bilinear": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p]),
+    "nerfart_mesh_sample_workspace_bytes": (_ll, [_i]),
+    "nerfart_mesh_sample_count": (_i, [_p, _p, _i, _i, _d, _i, _p, _ll, _p, _p]),
+    "nerfart_mesh_sample_emit": (_i, [_p, _p, _i, _i, _i, _p, _ll, _p, _p, _i, _p]),
+    "nerfart_mesh_grid_workspace_bytes": (_ll, [_i, _i, _i]),
+    "nerfart_mesh_grid_count": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _ll, _p, _p]),
+    "nerfart_mesh_grid_fill": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _ll, _p, _ll, _p]),
+    "nerfart_mesh_closest": (_i, [_p, _i, _p, _p, _i, _i, _i, _i, _i, _p, _ll, _p, _ll, _d, _p, _p, _p, _p]),
     "nerfart_band_workspace_bytes": (_ll, [_i, _i]),
     "nerfart_band_probe_points": (_i, [_i, _i, _d, _d, _p, _p]),
     "nerfart_band_select": (_i, [_i, _p, _f, _f, _i, _i, _p, _p, _p, _p, _p, _ll, _p, _p]),
@@ -526,6 +533,112 @@ def mesh_simplify_emit(verts, faces, dims, factor: int, reg: float, ws, cluster,
     _check(lib.nerfart_mesh_simplify_emit(fp, V, F, *grid, float(reg), _dev(ws, torch.uint8, "ws"), ws.numel(), _dev(cluster, torch.int32, "cluster"),
                                           out_v.data_ptr(), out_f.data_ptr(), int(V_out), int(F_out), _stream()), "nerfart_mesh_simplify_emit")
     return out_v, out_f
+
+
+def _mesh_arrays(verts, faces):
+    if verts.dim() != 2 or verts.shape[1] != 3:
+        raise NerfartHipError(f"verts must be [V, 3] (got {tuple(verts.shape)})")
+    V = int(verts.shape[0])
+    fp, F = _mesh_faces(faces, V)
+    return _dev(verts, name="verts"), fp, V, F
+
+
+def mesh_sample_workspace_bytes(F: int) -> int:
+    """nerfart_mesh_sample_workspace_bytes; F >= 2^31 raises with the library's message."""
+    n = int(lib.nerfart_mesh_sample_workspace_bytes(int(F)))
+    _check(0 if n else 2, "nerfart_mesh_sample_workspace_bytes")
+    return n
+
+
+def mesh_sample_count(verts, faces, density: float, seed: int, ws=None, info=None):
+    """nerfart_mesh_sample_count: (ws, info) - the filled workspace (uint8; a caller's own or a fresh one: it must stay untouched until
+    mesh_sample_emit has run) and the int32 device tensor info [4] = (n, bad faces, overflow flag, 0).  No host synchronisation."""
+    vp, fp, V, F = _mesh_arrays(verts, faces)
+    if ws is None:
+        ws = torch.empty(mesh_sample_workspace_bytes(F), dtype=torch.uint8, device=verts.device)
+    if info is None:
+        info = torch.empty(4, dtype=torch.int32, device=verts.device)
+    if tuple(info.shape) != (4,):
+        raise NerfartHipError(f"info must be [4] (got {tuple(info.shape)})")
+    _check(lib.nerfart_mesh_sample_count(vp, fp, V, F, float(density), int(seed) & 0xffffffff, _dev(ws, torch.uint8, "ws"), ws.numel(),
+                                         _dev(info, torch.int32, "info"), _stream()), "nerfart_mesh_sample_count")
+    return ws, info
+
+
+def mesh_sample_offsets(ws, F: int):
+    """off [F] int32: the offset of every face's first sample, out of the workspace mesh_sample_count filled (a copy)."""
+    return ws[:8 * int(F)].view(torch.int32).view(int(F), 2)[:, 0].clone()
+
+
+def mesh_sample_emit(verts, faces, seed: int, ws, n: int, points=None, face=None):
+    """nerfart_mesh_sample_emit: (points [n, 3] float32, face [n] int32) - the caller's own arrays or fresh ones - from the workspace
+    mesh_sample_count filled for the same mesh and seed."""
+    vp, fp, V, F = _mesh_arrays(verts, faces)
+    n = int(n)
+    if points is None:
+        points = torch.empty(n, 3, dtype=torch.float32, device=verts.device)
+    if face is None:
+        face = torch.empty(n, dtype=torch.int32, device=verts.device)
+    if tuple(points.shape) != (n, 3) or tuple(face.shape) != (n,):
+        raise NerfartHipError(f"points must be [{n}, 3] and face [{n}] (got {tuple(points.shape)}, {tuple(face.shape)})")
+    _check(lib.nerfart_mesh_sample_emit(vp, fp, V, F, int(seed) & 0xffffffff, _dev(ws, torch.uint8, "ws"), ws.numel(), _dev(points, name="points"),
+                                        _dev(face, torch.int32, "face"), n, _stream()), "nerfart_mesh_sample_emit")
+    return points, face
+
+
+def mesh_grid_workspace_bytes(grid) -> int:
+    """nerfart_mesh_grid_workspace_bytes; a refusal (a dimension outside 1 .. 1024, more than 2^24 cells) raises with the library's message."""
+    n = int(lib.nerfart_mesh_grid_workspace_bytes(*[int(g) for g in grid]))
+    _check(0 if n else 2, "nerfart_mesh_grid_workspace_bytes")
+    return n
+
+
+class MeshGrid:
+    """What nerfart_mesh_closest needs of a mesh: the grid, its filled workspace, the per-cell face lists, and the two numbers the host read."""
+    __slots__ = ("grid", "ws", "list", "entries", "good")
+
+
+def mesh_grid_build(verts, faces, grid) -> MeshGrid:
+    """nerfart_mesh_grid_count, ONE host read (entries, good faces), nerfart_mesh_grid_fill."""
+    vp, fp, V, F = _mesh_arrays(verts, faces)
+    if len(grid) != 3:
+        raise NerfartHipError(f"the grid must be (gx, gy, gz) (got {tuple(grid)})")
+    g = MeshGrid()
+    g.grid = tuple(int(x) for x in grid)
+    g.ws = torch.empty(mesh_grid_workspace_bytes(g.grid), dtype=torch.uint8, device=verts.device)
+    info = torch.empty(2, dtype=torch.int64, device=verts.device)
+    _check(lib.nerfart_mesh_grid_count(vp, fp, V, F, *g.grid, g.ws.data_ptr(), g.ws.numel(), info.data_ptr(), _stream()), "nerfart_mesh_grid_count")
+    g.entries, g.good = (int(c) for c in info.cpu())
+    if g.entries >= 1 << 31:
+        raise NerfartHipError(f"mesh_grid_build: {g.entries} entries in a grid of {g.grid} (2^31 or more): use a coarser grid")
+    g.list = torch.empty(g.entries, dtype=torch.int32, device=verts.device)
+    _check(lib.nerfart_mesh_grid_fill(vp, fp, V, F, *g.grid, g.ws.data_ptr(), g.ws.numel(), g.list.data_ptr(), g.entries, _stream()),
+           "nerfart_mesh_grid_fill")
+    return g
+
+
+def mesh_closest(points, verts, faces, g: MeshGrid, max_distance: float = float("inf"), want_visited: bool = False, dist=None, face=None, visited=None):
+    """nerfart_mesh_closest: (dist [n] float32, face [n] int32[, visited [n] int32]) for points [n, 3] float32 against the mesh mesh_grid_build
+    was given.  dist / face / visited: the caller's own arrays or fresh ones; visited is returned when asked for or given."""
+    vp, fp, V, F = _mesh_arrays(verts, faces)
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise NerfartHipError(f"points must be [n, 3] (got {tuple(points.shape)})")
+    n = int(points.shape[0])
+    pp = _dev(points, name="points")
+    if dist is None:
+        dist = torch.empty(n, dtype=torch.float32, device=verts.device)
+    if face is None:
+        face = torch.empty(n, dtype=torch.int32, device=verts.device)
+    if tuple(dist.shape) != (n,) or tuple(face.shape) != (n,):
+        raise NerfartHipError(f"dist and face must be [{n}] (got {tuple(dist.shape)}, {tuple(face.shape)})")
+    if visited is None and want_visited:
+        visited = torch.empty(n, dtype=torch.int32, device=verts.device)
+    if visited is not None and tuple(visited.shape) != (n,):
+        raise NerfartHipError(f"visited must be [{n}] (got {tuple(visited.shape)})")
+    _check(lib.nerfart_mesh_closest(pp, n, vp, fp, V, F, *g.grid, g.ws.data_ptr(), g.ws.numel(), g.list.data_ptr(), g.entries, float(max_distance),
+                                    _dev(dist, name="dist"), _dev(face, torch.int32, "face"), _dev(visited, torch.int32, "visited"), _stream()),
+           "nerfart_mesh_closest")
+    return (dist, face) if visited is None else (dist, face, visited)
 
 
 def mesh_atlas_layout(F: int, P: int):

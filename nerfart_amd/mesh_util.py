@@ -28,7 +28,9 @@ a textured mesh - OBJ, MTL, PNG (`write_obj`) - instead of the PLY: `bake_textur
 and colours every texel at its own point, `texel_points` says where that is (csrc/mesh_texture.hip).
 `rasterize` / `render_mesh` look at the mesh that came out, through a rend_util.get_rays camera (csrc/mesh_raster.hip): exact
 integer coverage, a depth test by integer atomics, per-pixel face / barycentrics / depth / normal, then per-vertex colours or the baked texture.
-`read_ply` / `read_obj` read back the files `write_ply` / `write_obj` write.  None of it is on the render or train path.
+`read_ply` / `read_obj` read back the files `write_ply` / `write_obj` write.  `sample_surface` / `closest_on_mesh` / `mesh_distance` say how far one
+mesh is from another - Chamfer, Hausdorff, F-score - from area-weighted samples and exact closest-point queries (csrc/mesh_distance.hip;
+tools/compare_mesh.py).  None of it is on the render or train path.
 """
 import types
 
@@ -636,6 +638,123 @@ def render_mesh(verts, faces, c2w, intrinsics, H: int, W: int, colors=None, uv=N
         rgb = torch.where(hit, rgb, torch.tensor(bg, dtype=torch.float32, device=dev))
     extras = {"mask_mesh": mask.bool(), "normals_mesh": n_mesh, "face_id": face_id, "bary": bary, "n_skipped": r["n_skipped"]}
     return rgb, r["depth"], extras
+
+
+DISTANCE_GRID_MAX = 256      # cells per axis of closest_on_mesh's default grid (256^3 = the 2^24 cells csrc/mesh_distance.hip accepts)
+
+
+def _distance_mesh(verts, faces, who, names=("verts", "faces")):
+    """The refusals the distance functions share, by name: tensors on the GPU, [V, 3] float32 and [F, 3] int32, contiguous."""
+    for t, name, dtype in ((verts, names[0], torch.float32), (faces, names[1], torch.int32)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise ValueError(f"{who}: {name} must be a tensor on the GPU (there is no CPU path)")
+        if t.dtype != dtype:
+            raise ValueError(f"{who}: {name} must be {dtype} (got {t.dtype})")
+        if t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError(f"{who}: {name} must be [n, 3] (got {tuple(t.shape)})")
+    if verts.device != faces.device:
+        raise ValueError(f"{who}: {names[0]} and {names[1]} must be on the same device (got {verts.device}, {faces.device})")
+    return verts.contiguous(), faces.contiguous()
+
+
+def default_distance_grid(F: int):
+    """The grid closest_on_mesh builds when none is given: g = ceil(sqrt(F / 8)) cells per axis, at most DISTANCE_GRID_MAX - a surface of F faces
+    occupies a few g^2 of the g^3 cells, which leaves a handful of faces per occupied cell.  A heuristic for speed only: the answer does not
+    depend on the grid."""
+    g = int(min(max(int(np.ceil(np.sqrt(max(int(F), 1) / 8.0))), 1), DISTANCE_GRID_MAX))
+    return (g, g, g)
+
+
+@torch.no_grad()
+def sample_surface(verts, faces, n=None, density=None, seed: int = 0):
+    """Area-weighted random points on the mesh (verts [V, 3] float32, faces [F, 3] int32, on the GPU): (points [N, 3] float32, face [N] int32), face
+    by face (csrc/mesh_distance.hip; the rules are in include/nerfart_hip.h).  Give the density (samples per unit area) or n, which makes the
+    density n / total area (the areas summed by torch in float64): N is then n in expectation, not exactly - every face f draws
+    floor(density area_f + h(seed, f)) samples, independently of every other face, so that a set of samples is a pure function of (mesh, density,
+    seed).  A face with an index outside [0, V) or a non-finite vertex gets no samples.  One host read (N)."""
+    from . import hip
+    verts, faces = _distance_mesh(verts, faces, "sample_surface")
+    if (n is None) == (density is None):
+        raise ValueError("sample_surface: give n or density, not both")
+    if density is None:
+        if int(n) < 0:
+            raise ValueError(f"sample_surface: n must be >= 0 (got {n})")
+        V = int(verts.shape[0])
+        idx = faces.long()
+        ok = ((idx >= 0) & (idx < V)).all(1)
+        tri = verts.double()[idx[ok]] if V else verts.new_zeros((0, 3, 3), dtype=torch.float64)
+        tri = tri[torch.isfinite(tri).reshape(-1, 9).all(1)]
+        area = 0.5 * torch.linalg.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]).norm(dim=1).sum()
+        area = float(area)
+        density = float(n) / area if area > 0.0 else 0.0
+    if not (np.isfinite(density) and density >= 0.0):
+        raise ValueError(f"sample_surface: the density must be finite and >= 0 (got {density})")
+    ws, info = hip.mesh_sample_count(verts, faces, density, seed)
+    N, _, overflow, _ = (int(c) for c in info.cpu())
+    if overflow:
+        raise ValueError(f"sample_surface: density {density} asks for 2^31 samples or more")
+    return hip.mesh_sample_emit(verts, faces, seed, ws, N)
+
+
+@torch.no_grad()
+def closest_on_mesh(points, verts, faces, max_distance: float = float("inf"), grid=None):
+    """For every point [n, 3] (float32, on the GPU) the distance to the mesh and the face that attains it: (dist [n] float32, face [n] int32) -
+    the exact minimum over all faces, computed in float64 and rounded once; ties go to the lowest face index (csrc/mesh_distance.hip).  A point
+    farther than max_distance reports (max_distance, -1), and so does every point when the mesh has no usable face.  grid = (gx, gy, gz) sets the
+    broad phase's uniform grid (default: default_distance_grid); the answer does not depend on it.  One host read (the grid's entries)."""
+    from . import hip
+    verts, faces = _distance_mesh(verts, faces, "closest_on_mesh")
+    if not torch.is_tensor(points) or not points.is_cuda:
+        raise ValueError("closest_on_mesh: points must be a tensor on the GPU (there is no CPU path)")
+    if points.dtype != torch.float32:
+        raise ValueError(f"closest_on_mesh: points must be torch.float32 (got {points.dtype})")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"closest_on_mesh: points must be [n, 3] (got {tuple(points.shape)})")
+    if not float(max_distance) >= 0.0:
+        raise ValueError(f"closest_on_mesh: max_distance must be >= 0 (got {max_distance})")
+    g = hip.mesh_grid_build(verts, faces, default_distance_grid(int(faces.shape[0])) if grid is None else grid)
+    return hip.mesh_closest(points.contiguous(), verts, faces, g, max_distance)
+
+
+def _direction_stats(d, threshold):
+    d = d.double()
+    if d.numel() == 0:
+        return {"n": 0, "mean": 0.0, "rms": 0.0, "max": 0.0, "within": None if threshold is None else 0.0}
+    return {"n": int(d.numel()), "mean": float(d.mean()), "rms": float((d * d).mean().sqrt()), "max": float(d.max()),
+            "within": None if threshold is None else int((d <= float(threshold)).sum()) / int(d.numel())}      # an integer count: exactly 1 when all are
+
+
+def distance_summary(d_ab, d_ba, threshold=None):
+    """The dict mesh_distance returns, from the per-sample distances of the two directions (tensors; reduced by torch in float64)."""
+    ab, ba = _direction_stats(d_ab, threshold), _direction_stats(d_ba, threshold)
+    out = {"a_to_b": ab, "b_to_a": ba, "chamfer": 0.5 * (ab["mean"] + ba["mean"]), "hausdorff": max(ab["max"], ba["max"]),
+           "threshold": None if threshold is None else float(threshold), "precision": ab["within"], "recall": ba["within"], "fscore": None}
+    if threshold is not None:
+        s = ab["within"] + ba["within"]
+        out["fscore"] = 2.0 * ab["within"] * ba["within"] / s if s > 0.0 else 0.0
+    return out
+
+
+@torch.no_grad()
+def mesh_distance(verts_a, faces_a, verts_b, faces_b, samples: int = 1 << 20, threshold=None, max_distance: float = float("inf"), seed: int = 0):
+    """How far surface A is from surface B: about `samples` area-weighted points of each (sample_surface, the same seed) and their exact distances
+    to the other mesh (closest_on_mesh).  dict:
+      a_to_b, b_to_a   per direction n (samples drawn), mean, rms, max (the one-sided Hausdorff distance) and within (the share of samples with
+                       distance <= threshold; None without a threshold);
+      chamfer          the mean of the two means;      hausdorff   the larger of the two maxima;
+      precision        a_to_b's within (A as the prediction, B as the truth), recall = b_to_a's, fscore = their harmonic mean.
+    A sample farther than max_distance counts as max_distance.  The reductions are torch's, in float64."""
+    verts_a, faces_a = _distance_mesh(verts_a, faces_a, "mesh_distance", ("verts_a", "faces_a"))
+    verts_b, faces_b = _distance_mesh(verts_b, faces_b, "mesh_distance", ("verts_b", "faces_b"))
+    if int(samples) < 1:
+        raise ValueError(f"mesh_distance: samples must be >= 1 (got {samples})")
+    if threshold is not None and not float(threshold) >= 0.0:
+        raise ValueError(f"mesh_distance: threshold must be >= 0 (got {threshold})")
+    pa, _ = sample_surface(verts_a, faces_a, n=samples, seed=seed)
+    pb, _ = sample_surface(verts_b, faces_b, n=samples, seed=seed)
+    d_ab, _ = closest_on_mesh(pa, verts_b, faces_b, max_distance)
+    d_ba, _ = closest_on_mesh(pb, verts_a, faces_a, max_distance)
+    return distance_summary(d_ab, d_ba, threshold)
 
 
 def _check_extract_options(o):

@@ -12,7 +12,11 @@ host's clock - mesh_util.write_obj.  `--render H W` adds the rasteriser (csrc/me
 the model's frame, seen by scene.camera(H, W): the three raster stages each alone (nerfart_mesh_project, _raster, _resolve), mesh_util.rasterize as
 a whole (with its one host read), and the shading calls - nerfart_mesh_interp of per-corner UVs and nerfart_mesh_sample_bilinear on an atlas of
 patch --texture (default 4) filled with noise: the sampling cost does not depend on what the texels hold.  DESIGN.md 4.7 says which of these
-figures have been taken."""
+figures have been taken.  `--distance [--distance_samples S]` (with --simplify) adds the mesh distance (csrc/mesh_distance.hip) of the simplified mesh
+against marching cubes' own, in grid cells: the stages each alone - sampling (nerfart_mesh_sample_count, _emit), the grid build of the undecimated
+mesh (nerfart_mesh_grid_count + _fill, with its host read) and the query (nerfart_mesh_closest) of S samples of the simplified mesh -,
+mesh_util.mesh_distance as a whole (both directions), and the distances it found; with --narrow_band also the distance between the banded
+sweep's mesh and the dense one."""
 import argparse, json, os, statistics, sys, tempfile, time
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -43,7 +47,11 @@ def main():
     ap.add_argument("--texture", type=int, default=None, help="also time the texture bake (mesh_util.bake_texture) with this patch size")
     ap.add_argument("--texture_project", type=int, default=2, help="projection steps of --texture")
     ap.add_argument("--render", type=int, nargs=2, default=None, metavar=("H", "W"), help="also time the rasteriser on the extracted mesh at this image size")
+    ap.add_argument("--distance", action="store_true", help="also time mesh_util.mesh_distance of the simplified mesh against the extracted one (needs --simplify)")
+    ap.add_argument("--distance_samples", type=int, default=1 << 20)
     args = ap.parse_args()
+    if args.distance and not args.simplify:
+        ap.error("--distance compares the simplified mesh with the extracted one: give --simplify C")
     from nerfart_amd import scene, mesh_util, hip
     dev = torch.device("cuda", 0)
     model, _, _ = scene.build_model("VolSDF", seed=0, beta=0.01, device=dev, precision="mixed")
@@ -70,6 +78,9 @@ def main():
         res["mesh_equal"] = False                                  # stays False if the banded volume raises in marching_cubes
         bverts, bfaces = mesh_util.marching_cubes(bvol, 0.0, spacing=[vs / N] * 3, origin=[-vs / 2] * 3)
         res["mesh_equal"] = bool(torch.equal(verts.view(torch.int32), bverts.view(torch.int32)) and torch.equal(faces, bfaces))
+        if args.distance:
+            d = mesh_util.mesh_distance(bverts, bfaces, verts, faces, samples=args.distance_samples)
+            res["distance_banded_vs_dense"] = {"chamfer": d["chamfer"], "hausdorff": d["hausdorff"]}
         del bvol, verts, faces, bverts, bfaces
         res["banded_volume_ms"], _ = timed(banded, max(3, args.iters // 4))
         res.update(band_brick=args.band_brick, band_lipschitz=mesh_util.BAND_LIPSCHITZ, evaluated_share=round(info["evaluated_points"] / N ** 3, 5),
@@ -86,6 +97,21 @@ def main():
                                            args.iters)
         res.update(simplify_factor=c, simplified_vertices=int(out_v.shape[0]), simplified_triangles=int(out_f.shape[0]),
                    simplify_workspace_MiB=round(sws.numel() / 2 ** 20, 1))
+    if args.distance:                                              # the simplified mesh against the extracted one, in grid cells
+        S, seed = args.distance_samples, 0
+        grid = mesh_util.default_distance_grid(F)
+        sample = lambda: mesh_util.sample_surface(out_v, out_f, n=S, seed=seed)
+        points, _ = sample()                                       # warm-ups
+        g = hip.mesh_grid_build(gverts, gfaces, grid)
+        hip.mesh_closest(points, gverts, gfaces, g)
+        res["distance_sample_ms"], _ = timed(sample, args.iters)
+        res["distance_grid_build_ms"], _ = timed(lambda: hip.mesh_grid_build(gverts, gfaces, grid), args.iters)
+        res["distance_closest_ms"], (dist, _, visited) = timed(lambda: hip.mesh_closest(points, gverts, gfaces, g, want_visited=True), args.iters)
+        res["distance_total_ms"], d = timed(lambda: mesh_util.mesh_distance(out_v, out_f, gverts, gfaces, samples=S, threshold=0.5, seed=seed),
+                                            max(3, args.iters // 4))
+        res.update(distance_samples=int(points.shape[0]), distance_grid=list(grid), distance_entries=g.entries,
+                   distance_grid_workspace_MiB=round(g.ws.numel() / 2 ** 20, 1), distance_faces_tested_mean=float(visited.double().mean()),
+                   distance_faces_tested_max=int(visited.max()), distance_unit="grid cells", distance=d)
     if args.texture:                                               # the bake of the final mesh, in the model's frame
         P, K, c = args.texture, args.texture_project, args.simplify or 1
         if args.simplify:
