@@ -158,10 +158,11 @@ __device__ __forceinline__ float error_bound_scan_cached(const float* d, const f
 // d*_k and delta^2 do not.  Loaded once per ray (the one stride-seg pass over the LDS rows that is left: lane l's addresses l * seg + i put up to 32
 // lanes on a bank), after which a scan touches no LDS at all.  scan_consts is error_bound_scan_cached with its first pass's loads and
 // beta-independent arithmetic hoisted: the same operations on the same values in the same order (delta * delta and 0.5 (|s_k| + |s_k+1| - delta)
-// are not contractable into their consumers), i.e. the same bits - tests/test_gpu_guarded_sampler.py::test_cached_scan_equals_generic_scan holds
-// whole frames equal to the generic form.
+// are not contractable into their consumers), i.e. the same bits.  The two products of t = alpha / (4 beta) * (delta * delta) are two multiplications
+// either way and are formed again where they are used instead of being kept (48 VGPRs at 24 intervals per lane: k_merge_check 194 -> 146, 3 waves
+// per SIMD instead of 2) - tests/test_gpu_guarded_sampler.py::test_cached_scan_equals_generic_scan holds whole frames equal to the generic form.
 template <int MAXSEG>
-struct SegConsts { float delta[MAXSEG], s[MAXSEG], dstar[MAXSEG], dd[MAXSEG]; int cnt; };
+struct SegConsts { float delta[MAXSEG], s[MAXSEG], dstar[MAXSEG]; int cnt; };
 
 template <int MAXSEG>
 __device__ __forceinline__ void load_seg_consts(const float* d, const float* s, int n, SegConsts<MAXSEG>& C) {
@@ -175,32 +176,38 @@ __device__ __forceinline__ void load_seg_consts(const float* d, const float* s, 
     if (k0 < k1) { dk = d[k0]; sk = s[k0]; }
 #pragma unroll
     for (int i = 0; i < MAXSEG; ++i) {
-        C.delta[i] = 0.f; C.s[i] = 0.f; C.dstar[i] = 0.f; C.dd[i] = 0.f;
+        C.delta[i] = 0.f; C.s[i] = 0.f; C.dstar[i] = 0.f;
         if (i < C.cnt) {
             const float dn = d[k0 + i + 1], sn = s[k0 + i + 1];
             const float delta = dn - dk;
             C.delta[i] = delta;
             C.s[i] = sk;
             C.dstar[i] = fmaxf(0.5f * (fabsf(sk) + fabsf(sn) - delta), 0.f);
-            C.dd[i] = delta * delta;
             dk = dn; sk = sn;
         }
     }
 }
 
+// v * v, multiplied at this very place: the empty asm makes the value opaque, so the compiler neither hoists the product out of the bisection loop
+// nor carries it from the first pass to the second - either would keep MAXSEG more registers alive across the scan
+__device__ __forceinline__ float squared_here(float v) {
+    asm volatile("" : "+v"(v));
+    return v * v;
+}
+
 template <int MAXSEG>
 __device__ __forceinline__ float scan_consts(const SegConsts<MAXSEG>& C, float alpha, float beta) {
     const float a4b = alpha / (4.f * beta);
-    float c_sigma[MAXSEG], c_t[MAXSEG], c_x[MAXSEG];
+    float c_sigma[MAXSEG], c_x[MAXSEG];
     float sR = 0.f, sE = 0.f;
 #pragma unroll
     for (int i = 0; i < MAXSEG; ++i) {
-        c_sigma[i] = 0.f; c_t[i] = 0.f; c_x[i] = 0.f;
+        c_sigma[i] = 0.f; c_x[i] = 0.f;
         if (i < C.cnt) {
             const float sg = sdf_to_sigma(C.s[i], alpha, beta);
-            const float t = a4b * C.dd[i];
+            const float t = a4b * squared_here(C.delta[i]);
             const float x = expf(-C.dstar[i] / beta);
-            c_sigma[i] = sg; c_t[i] = t; c_x[i] = x;
+            c_sigma[i] = sg; c_x[i] = x;
             sR = __fmaf_rn(C.delta[i], sg, sR);
             sE = __fmaf_rn(t, x, sE);
         }
@@ -210,7 +217,7 @@ __device__ __forceinline__ float scan_consts(const SegConsts<MAXSEG>& C, float a
 #pragma unroll
     for (int i = 0; i < MAXSEG; ++i) {
         if (i < C.cnt) {
-            E = __fmaf_rn(c_t[i], c_x[i], E);
+            E = __fmaf_rn(a4b * squared_here(C.delta[i]), c_x[i], E);
             float b = expf(-R) * (expf(E) - 1.f);
             if (isnan(b)) b = INFINITY;
             mx = fmaxf(mx, b);
@@ -220,15 +227,26 @@ __device__ __forceinline__ float scan_consts(const SegConsts<MAXSEG>& C, float a
     return wave_max(mx);
 }
 
+// Which form scans a row of n samples: the smallest MAXSEG of 8 (512 samples: the first check), 16 (1,024: round 1, every undecided ray of a frame)
+// and 24 (1,536: round 2, 78 % of them) that holds a lane's segment, else 0 = the generic form.  n is the same for every ray of a launch, so the
+// HOST picks and launches the kernel built for that form alone (error_bound_scan<MAXSEG>): a kernel with all four behind a branch runs every row
+// length with the registers of the 24-interval form.
+inline int scan_maxseg(int n) {
+#ifndef NERFART_SCAN_GENERIC
+    const int seg = (n - 1 + 63) >> 6;
+    if (seg <= 8) return 8;
+    if (seg <= 16) return 16;
+    if (seg <= 24) return 24;
+#endif
+    (void)n;
+    return 0;
+}
+
+template <int MAXSEG>
 __device__ __forceinline__ float error_bound_scan(const float* d, const float* s, int n, float alpha, float beta,
                                                   float* w_out, bool clamp) {
-#ifndef NERFART_SCAN_GENERIC
-    const int seg = (n - 1 + 63) >> 6;                       // wave-uniform: n is
-    if (seg <= 8) return error_bound_scan_cached<8>(d, s, n, alpha, beta, w_out, clamp);          // 512 samples: the first check
-    if (seg <= 16) return error_bound_scan_cached<16>(d, s, n, alpha, beta, w_out, clamp);        // 1,024: round 1 (every undecided ray of a frame)
-    if (seg <= 24) return error_bound_scan_cached<24>(d, s, n, alpha, beta, w_out, clamp);        // 1,536: round 2 (78 % of them)
-#endif
-    return error_bound_scan_generic(d, s, n, alpha, beta, w_out, clamp);
+    if constexpr (MAXSEG > 0) return error_bound_scan_cached<MAXSEG>(d, s, n, alpha, beta, w_out, clamp);
+    else return error_bound_scan_generic(d, s, n, alpha, beta, w_out, clamp);
 }
 
 // cdf[0] = 0, cdf[k+1] = 1 - exp(-R_t[k]) with R_t[k] = sum_{i<k} sigma_i delta_i, k = 0..n-2

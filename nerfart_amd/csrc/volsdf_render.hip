@@ -71,7 +71,8 @@ __device__ __forceinline__ void emit_final_samples(const float* d, const float* 
 }
 
 // Round 0: bound check of the initial 512 uniform samples at the net's beta (volsdf.py:159-177).
-// Converged rays get their 64 fine samples now; the others are queued with beta+ = beta+_0.
+// Converged rays get their 64 fine samples now; the others are queued with beta+ = beta+_0.  MAXSEG: ray_common.h::scan_maxseg(n).
+template <int MAXSEG>
 __global__ void __launch_bounds__(64)
 k_first_check(SamplerParams P, const float* __restrict__ dA, const float* __restrict__ sA,
               const float* __restrict__ u_final, float beta_plus0_denom, const float* __restrict__ far,
@@ -83,7 +84,7 @@ k_first_check(SamplerParams P, const float* __restrict__ dA, const float* __rest
     load_row(d, dA + (size_t)ray * P.cap, P.n);
     load_row(s, sA + (size_t)ray * P.cap, P.n);
     __syncthreads();
-    const float mx = error_bound_scan(d, s, P.n, P.alpha_net, P.beta_net, nullptr, false);
+    const float mx = error_bound_scan<MAXSEG>(d, s, P.n, P.alpha_net, P.beta_net, nullptr, false);
     const float fr = far ? far[ray] : far_s;
     if (in_guard_band(P, mx)) { escalate(P, ray); return; }
     if (!(mx > P.eps)) {
@@ -101,6 +102,8 @@ k_first_check(SamplerParams P, const float* __restrict__ dA, const float* __rest
 // (sample_pdf(d, bounds, N_up + 2, det=True)[1:-1], volsdf.py:196), sorted.  The inversion of an ascending u over one CDF comes out ascending except
 // for last-place effects at bin boundaries and NaN rows: the 45-stage sort runs only for a row that fails lane_row_in_order (sample_cdf.h), or always
 // (always_sort: NERFART_UPSAMPLE_SORT=always) - the same bits either way.
+// MAXSEG: ray_common.h::scan_maxseg(n).
+template <int MAXSEG, bool S_IN_LDS>
 __global__ void __launch_bounds__(64)
 k_upsample(SamplerParams P, const float* __restrict__ dA, const float* __restrict__ sA,
            const int* __restrict__ act, const float* __restrict__ beta_plus, const float* __restrict__ u_up,
@@ -108,12 +111,15 @@ k_upsample(SamplerParams P, const float* __restrict__ dA, const float* __restric
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int slot = blockIdx.x, ray = act[slot];
     const int n = P.n;
-    float* d = sm; float* s = sm + n; float* cdf = sm + 2 * n; float* w = sm + 3 * n; float* out = sm + 4 * n;  // out: n_up
+    // LDS: d, cdf, w (n each), out (n_up).  The sdf row is read by the one error-bound scan only and stays in global memory: 3 n + n_up floats
+    // instead of 4 n + n_up - the kernel waits on occupancy.  S_IN_LDS: the earlier form, a copy of the row behind `out`.
+    float* d = sm; float* cdf = sm + n; float* w = sm + 2 * n; float* out = sm + 3 * n;
+    const float* s = sA + (size_t)ray * P.cap;
     load_row(d, dA + (size_t)ray * P.cap, n);
-    load_row(s, sA + (size_t)ray * P.cap, n);
+    if constexpr (S_IN_LDS) { float* sl = out + P.n_up; load_row(sl, s, n); s = sl; }
     __syncthreads();
     const float bp = beta_plus[ray];
-    error_bound_scan(d, s, n, 1.f / bp, bp, w, clamp_bounds != 0);
+    error_bound_scan<MAXSEG>(d, s, n, 1.f / bp, bp, w, clamp_bounds != 0);
     __syncthreads();
     // pdf = (w + 1e-5) / sum; cdf = [0, cumsum(pdf)]   (rend_util.py:260-265)
     // (round 6 b, measured and not kept: the bounds, the pdf and the running cdf of a lane's segment in registers instead of three passes over the LDS
@@ -135,28 +141,42 @@ k_upsample(SamplerParams P, const float* __restrict__ dA, const float* __restric
     for (int j = lane; j < P.n_up; j += 64) d_new[(size_t)slot * P.n_up + j] = out[j];
 }
 
-// What k_merge_check does once the merged rows are in LDS: the bound check at the net's beta, then sampling (converged) or the bisection for beta+.
+// What k_merge_check does once the merged rows exist: the bound check at the net's beta, then sampling (converged) or the bisection for beta+.
 // MAXSEG > 0: the lane's beta-independent interval constants are loaded once and every scan runs from registers (ray_common.h::SegConsts);
-// MAXSEG = 0: every scan through error_bound_scan (any row length; NERFART_SCAN_GENERIC builds this form everywhere).
-template <int MAXSEG>
-__device__ __forceinline__ void merge_check_tail(const SamplerParams& P, int ray, const float* d, const float* s, float* cdf, int nm,
+// MAXSEG = 0: every scan through the generic error-bound scan (any row length; NERFART_SCAN_GENERIC builds this form everywhere).
+// ROWS_IN_LDS (the earlier form): d, s = the merged rows in LDS, r0 = a third free row of nm floats (the cdf), r1 unused.
+// Otherwise d, s = the merged rows in GLOBAL memory (dB / sB, written by this workgroup and fenced) and r0, r1 = the only two LDS rows of nm
+// floats, both free: they take a copy of d, s (coalesced; a lane's segment read straight from global memory touches 64 cache lines per load),
+// from which the constants are loaded or the generic scans run; the converged path keeps d in r0, puts the cdf in r1 and reads s, twice and in
+// order, from global memory.  The same lane owns the same intervals in the same order.
+template <int MAXSEG, bool ROWS_IN_LDS>
+__device__ __forceinline__ void merge_check_tail(const SamplerParams& P, int ray, const float* d, const float* s, float* r0, float* r1, int nm,
                                                  const float* __restrict__ u_final, float* __restrict__ d_fine, float* __restrict__ beta_plus,
                                                  float* __restrict__ beta_map, float* __restrict__ iter_usage, int* __restrict__ act_out,
                                                  int* __restrict__ act_count) {
     constexpr int NS = MAXSEG > 0 ? MAXSEG : 1;
+    const float *dl = d, *sl = s;                                 // the merged rows in LDS
+    if constexpr (!ROWS_IN_LDS) { load_row(r0, d, nm); load_row(r1, s, nm); __syncthreads(); dl = r0; sl = r1; }
     SegConsts<NS> C;
-    if constexpr (MAXSEG > 0) load_seg_consts<NS>(d, s, nm, C);
+    if constexpr (MAXSEG > 0) load_seg_consts<NS>(dl, sl, nm, C);
     auto scan = [&](float alpha, float beta) -> float {
         if constexpr (MAXSEG > 0) return scan_consts<NS>(C, alpha, beta);
-        else return error_bound_scan(d, s, nm, alpha, beta, nullptr, false);
+        else return error_bound_scan<0>(dl, sl, nm, alpha, beta, nullptr, false);
     };
     const float mx = scan(P.alpha_net, P.beta_net);
     if (in_guard_band(P, mx)) { escalate(P, ray); return; }
     if (!(mx > P.eps)) {
-        // cdf = the two depth rows of the merge: dead by now, exactly n + nu = nm floats
-        opacity_cdf(d, s, nm, P.alpha_net, P.beta_net, cdf);
-        __syncthreads();
-        emit_final_samples(d, cdf, nm, u_final + (size_t)ray * P.u_final_stride, P.n_final, d_fine + (size_t)ray * P.n_final);
+        if constexpr (ROWS_IN_LDS) {
+            // cdf = the two depth rows of the merge: dead by now, exactly n + nu = nm floats
+            opacity_cdf(d, s, nm, P.alpha_net, P.beta_net, r0);
+            __syncthreads();
+            emit_final_samples(d, r0, nm, u_final + (size_t)ray * P.u_final_stride, P.n_final, d_fine + (size_t)ray * P.n_final);
+        } else {
+            __syncthreads();                                      // r0 holds d; nobody reads the copy of s in r1 any more
+            opacity_cdf(r0, s, nm, P.alpha_net, P.beta_net, r1);
+            __syncthreads();
+            emit_final_samples(r0, r1, nm, u_final + (size_t)ray * P.u_final_stride, P.n_final, d_fine + (size_t)ray * P.n_final);
+        }
         if (threadIdx.x == 0) { iter_usage[ray] = (float)P.it; beta_map[ray] = P.beta_net; }
     } else {
         float hi = beta_plus[ray], lo = P.beta_net;
@@ -174,19 +194,26 @@ __device__ __forceinline__ void merge_check_tail(const SamplerParams& P, int ray
 
 // Merge the 512 new (depth, sdf) pairs into the ray's sorted sample set, re-check the bound at the
 // net's beta; converged -> 64 fine samples; else bisection for beta+ and re-queue (volsdf.py:211-285).
+// One kernel per scan form (MAXSEG: merge_check_tail; merge_check_kernel picks it from the row length): as one kernel with a branch, every round
+// ran with the 194 VGPRs of the 24-interval register scan - 2 waves per SIMD, 8 rays per CU, whatever the LDS allowed.
+// LDS: the two depth rows (searched by the rank merge) and ONE more row of n + n_up floats: 2 (n + n_up) floats per ray.  The merged (d, s) pairs go
+// straight to dB / sB - the next round reads them there anyway - and come back as the scans' copy in the same two rows (merge_check_tail).  The
+// sdf values are read once each, from global memory.  ROWS_IN_LDS: the earlier form (NERFART_PERRAY_LDS=ref), the merged rows behind the depth
+// rows, 3 (n + n_up) floats: 13 / 8 / 6 rays per CU in rounds 1 / 2 / 3 where the registers allow 16 / 12 / 32.
+template <int MAXSEG, bool ROWS_IN_LDS>
 __global__ void __launch_bounds__(64)
-k_merge_check(SamplerParams P, const float* __restrict__ dA, const float* __restrict__ sA,
-              float* __restrict__ dB, float* __restrict__ sB, const int* __restrict__ act,
-              const float* __restrict__ d_new, const float* __restrict__ s_new, const float* __restrict__ u_final,
-              float* __restrict__ d_fine, float* __restrict__ beta_plus, float* __restrict__ beta_map,
-              float* __restrict__ iter_usage, int* __restrict__ act_out, int* __restrict__ act_count) {
+k_merge_check(SamplerParams P, const float* __restrict__ dA, const float* __restrict__ sA, float* dB, float* sB, const int* __restrict__ act,
+              const float* __restrict__ d_new, const float* __restrict__ s_new, const float* __restrict__ u_final, float* __restrict__ d_fine,
+              float* __restrict__ beta_plus, float* __restrict__ beta_map, float* __restrict__ iter_usage, int* __restrict__ act_out,
+              int* __restrict__ act_count) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int slot = blockIdx.x, ray = act[slot];
     const int n = P.n, nu = P.n_up, nm = n + nu;
-    // LDS: the two depth rows (searched), then the merged rows; the sdf values are read once each, straight from global memory
-    // (round 3: 3 (n + n_up) floats instead of 4 - one more ray per CU in every round; results unchanged)
     float* d_old = sm; float* dn = sm + n;
-    float* d = dn + nu; float* s = d + nm;       // merged
+    float* row1 = dn + nu;                       // nm floats
+    float* dg = dB + (size_t)ray * P.cap; float* sg = sB + (size_t)ray * P.cap;
+    float* d = ROWS_IN_LDS ? row1 : dg;          // merged
+    float* s = ROWS_IN_LDS ? row1 + nm : sg;
     const float* s_old = sA + (size_t)ray * P.cap;
     const float* sn = s_new + (size_t)slot * nu;
     load_row(d_old, dA + (size_t)ray * P.cap, n);
@@ -201,18 +228,12 @@ k_merge_check(SamplerParams P, const float* __restrict__ dA, const float* __rest
         const int r = k + upper_bound(d_old, n, dn[k]);
         d[r] = dn[k]; s[r] = sn[k];
     }
+    if constexpr (!ROWS_IN_LDS) __threadfence_block();            // the merged rows are read back below by other lanes
     __syncthreads();
-    for (int i = threadIdx.x; i < nm; i += 64) {
-        dB[(size_t)ray * P.cap + i] = d[i];
-        sB[(size_t)ray * P.cap + i] = s[i];
+    if constexpr (ROWS_IN_LDS) {
+        for (int i = threadIdx.x; i < nm; i += 64) { dg[i] = d[i]; sg[i] = s[i]; }
     }
-#ifndef NERFART_SCAN_GENERIC
-    // rounds 1 and 2 (1,024 / 1,536 merged samples: every undecided ray of a frame / 78 % of them): the check and the 10 bisection scans from registers
-    const int seg = (nm - 1 + 63) >> 6;
-    if (seg <= 16) { merge_check_tail<16>(P, ray, d, s, d_old, nm, u_final, d_fine, beta_plus, beta_map, iter_usage, act_out, act_count); return; }
-    if (seg <= 24) { merge_check_tail<24>(P, ray, d, s, d_old, nm, u_final, d_fine, beta_plus, beta_map, iter_usage, act_out, act_count); return; }
-#endif
-    merge_check_tail<0>(P, ray, d, s, d_old, nm, u_final, d_fine, beta_plus, beta_map, iter_usage, act_out, act_count);
+    merge_check_tail<MAXSEG, ROWS_IN_LDS>(P, ray, d, s, d_old, row1, nm, u_final, d_fine, beta_plus, beta_map, iter_usage, act_out, act_count);
 }
 
 // Rays still active after the last round: sample with the last beta+ (volsdf.py:294-300).
@@ -371,42 +392,35 @@ __global__ void k_gather_segment_depths(const int* __restrict__ live, int n_live
     c_d[i] = d_all[(size_t)live[slot] * P + e0 + j];
 }
 
-// slot-major compact outputs of a segment launch -> their [R, P] places
-__global__ void k_scatter_segment(const int* __restrict__ live, int n_live, int P, int e0, int len, const float* __restrict__ c_sdf,
-                                  const float* __restrict__ c_nabla, const float* __restrict__ c_rad, float* __restrict__ sdf,
-                                  float* __restrict__ nabla, float* __restrict__ rad) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long long)n_live * len) return;
-    const int slot = (int)(i / len), j = (int)(i - (long long)slot * len);
-    const size_t q = (size_t)live[slot] * P + e0 + j;
-    sdf[q] = c_sdf[i];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { nabla[3 * q + c] = c_nabla[3 * (size_t)i + c]; rad[3 * q + c] = c_rad[3 * (size_t)i + c]; }
-}
-
-// After segment [e0, e0 + len) is in place: one wave per live ray adds x_k, k = e0 .. e0 + len - 1 (every interval that starts inside the
-// segment; len <= SKIP_SEG < 64, and e0 + len < P here, so d_{k+1} exists), to the ray's running optical depth - lane j computes x_{e0+j}, the
-// sum itself runs in ascending k as one fp32 chain - and decides the rule above for s = e0 + len.  A ray found dead has its samples s .. P - 1
-// zero-filled.  alive[slot] = 0 / 1 feeds k_compact_live.
+// After a segment launch: one wave per live ray.  (1) The slot-major compact outputs of segment [e0, e0 + len) go to their [R, P] places.
+// (2) advance != 0 (every segment but the last; len <= SKIP_SEG < 64, and e0 + len < P, so d_{k+1} exists): the wave adds x_k, k = e0 .. e0 + len - 1
+// (every interval that starts inside the segment), to the ray's running optical depth - lane j computes x_{e0+j} from the sdf value it has just
+// placed, the sum itself runs in ascending k as one fp32 chain - and decides the rule above for s = e0 + len.  A ray found dead has its samples
+// s .. P - 1 zero-filled.  alive[slot] = 0 / 1 feeds k_compact_live.
 __global__ void __launch_bounds__(256)
-k_advance_live(const int* __restrict__ live, int n_live, int P, int e0, int len, const float* __restrict__ d_all, float alpha, float beta,
-               float* __restrict__ osum, int* __restrict__ alive, float* sdf, float* __restrict__ nabla, float* __restrict__ rad) {
+k_scatter_advance(const int* __restrict__ live, int n_live, int P, int e0, int len, int advance, const float* __restrict__ c_sdf,
+                  const float* __restrict__ c_nabla, const float* __restrict__ c_rad, const float* __restrict__ d_all, float alpha, float beta,
+                  float* __restrict__ osum, int* __restrict__ alive, float* __restrict__ sdf, float* __restrict__ nabla, float* __restrict__ rad) {
     const int slot = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (slot >= n_live) return;                                   // wave-uniform
     const int ray = live[slot];
+    const size_t c0 = (size_t)slot * len, q = (size_t)ray * P + e0;
+    float sk = 0.f;
+    if (lane < len) { sk = c_sdf[c0 + lane]; sdf[q + lane] = sk; }
+    for (int i = lane; i < 3 * len; i += 64) { nabla[3 * q + i] = c_nabla[3 * c0 + i]; rad[3 * q + i] = c_rad[3 * c0 + i]; }
+    if (!advance) return;
     const float* dr = d_all + (size_t)ray * P;
-    const float* sr = sdf + (size_t)ray * P;
     float x = 0.f;
     if (lane < len) {
         const int k = e0 + lane;
-        x = fmaxf(sdf_to_sigma(sr[k], alpha, beta) * (dr[k + 1] - dr[k]), 0.f);
+        x = fmaxf(sdf_to_sigma(sk, alpha, beta) * (dr[k + 1] - dr[k]), 0.f);
     }
     float sum = osum[ray];
     for (int j = 0; j < len; ++j) sum = __fadd_rn(sum, __shfl(x, j, 64));
     const bool dead = sum >= SKIP_THETA;
     if (lane == 0) { osum[ray] = sum; alive[slot] = dead ? 0 : 1; }
     if (dead) {
-        const size_t q0 = (size_t)ray * P + e0 + len;
+        const size_t q0 = q + len;
         const int n = P - (e0 + len);
         for (int i = lane; i < n; i += 64) sdf[q0 + i] = 0.f;
         for (int i = lane; i < 3 * n; i += 64) { nabla[3 * q0 + i] = 0.f; rad[3 * q0 + i] = 0.f; }
@@ -499,8 +513,10 @@ static int first_check_launch(int n_rays, int n, int cap, int n_final, float eps
     if (n_rays <= 0) return 0;
     SamplerParams P{n, cap, 0, n_final, 0, 0, eps, alpha_net, beta_net, u_final_stride, guard, esc_list, esc_count};
     const size_t lds = (size_t)3 * n * sizeof(float);
-    if (int rc = set_lds((const void*)k_first_check, lds, kLdsRefusal)) return rc;
-    hipLaunchKernelGGL(k_first_check, dim3(n_rays), dim3(64), lds, (hipStream_t)stream, P, dA, sA, u_final,
+    const int m = scan_maxseg(n);
+    auto* const kernel = m == 8 ? k_first_check<8> : m == 16 ? k_first_check<16> : m == 24 ? k_first_check<24> : k_first_check<0>;
+    if (int rc = set_lds((const void*)kernel, lds, kLdsRefusal)) return rc;
+    hipLaunchKernelGGL(kernel, dim3(n_rays), dim3(64), lds, (hipStream_t)stream, P, dA, sA, u_final,
                        beta_plus0_denom, far, far_s, d_fine, beta_plus, beta_map, iter_usage, act_out, act_count);
     NERFART_HIP(hipGetLastError());
     return 0;
@@ -516,17 +532,36 @@ int nerfart_volsdf_first_check(int n_rays, int n, int cap, int n_final, float ep
                               beta_plus, beta_map, iter_usage, act_out, act_count, 0.f, nullptr, nullptr, stream);
 }
 
+// NERFART_PERRAY_LDS=ref: k_upsample and k_merge_check in their earlier form, with the sdf row / the merged rows in LDS (one more row of LDS per ray,
+// the same bits).  Read at every call, so that one process can run both (tests/test_gpu_perray_lds.py).
+static bool perray_lds_ref() {
+    const char* e = std::getenv("NERFART_PERRAY_LDS");
+    return e != nullptr && e[0] == 'r';
+}
+
+typedef void (*upsample_fn)(SamplerParams, const float*, const float*, const int*, const float*, const float*, int, int, float*);
+static upsample_fn upsample_kernel(int maxseg, bool ref) {
+    switch (maxseg) {
+    case 8: return ref ? k_upsample<8, true> : k_upsample<8, false>;
+    case 16: return ref ? k_upsample<16, true> : k_upsample<16, false>;
+    case 24: return ref ? k_upsample<24, true> : k_upsample<24, false>;
+    default: return ref ? k_upsample<0, true> : k_upsample<0, false>;
+    }
+}
+
 static int upsample_launch(int n_active, int n, int cap, int n_up, const float* dA, const float* sA, const int* act,
                            const float* beta_plus, const float* u_up, int clamp_bounds, float* d_new, void* stream) {
     if (n_active <= 0) return 0;
     if (n_up & (n_up - 1)) { set_last_error("n_up must be a power of two"); return 2; }
     SamplerParams P{n, cap, n_up, 0, 0, 0, 0.f, 0.f, 0.f};
-    const size_t lds = ((size_t)4 * n + n_up) * sizeof(float);
-    if (int rc = set_lds((const void*)k_upsample, lds, kLdsRefusal)) return rc;
+    const bool ref = perray_lds_ref();
+    const size_t lds = ((size_t)(ref ? 4 : 3) * n + n_up) * sizeof(float);
+    const upsample_fn kernel = upsample_kernel(scan_maxseg(n), ref);
+    if (int rc = set_lds((const void*)kernel, lds, kLdsRefusal)) return rc;
     // NERFART_UPSAMPLE_SORT=always sorts every row; read at every call, so that one process can run both (tests/test_gpu_upsample_sorted.py)
     const char* e = std::getenv("NERFART_UPSAMPLE_SORT");
     const int always_sort = (e != nullptr && e[0] == 'a') ? 1 : 0;
-    hipLaunchKernelGGL(k_upsample, dim3(n_active), dim3(64), lds, (hipStream_t)stream, P, dA, sA, act, beta_plus, u_up,
+    hipLaunchKernelGGL(kernel, dim3(n_active), dim3(64), lds, (hipStream_t)stream, P, dA, sA, act, beta_plus, u_up,
                        clamp_bounds, always_sort, d_new);
     NERFART_HIP(hipGetLastError());
     return 0;
@@ -539,6 +574,16 @@ int nerfart_volsdf_upsample(int n_active, int n, int cap, int n_up, const float*
     return upsample_launch(n_active, n, cap, n_up, dA, sA, act, beta_plus, u_up, clamp_bounds, d_new, stream);
 }
 
+typedef void (*merge_check_fn)(SamplerParams, const float*, const float*, float*, float*, const int*, const float*, const float*, const float*, float*,
+                               float*, float*, float*, int*, int*);
+// rounds 1 and 2 (1,024 / 1,536 merged samples: every undecided ray of a frame / 78 % of them): the check and the 10 bisection scans from registers
+static merge_check_fn merge_check_kernel(int nm, bool ref) {
+    const int m = scan_maxseg(nm);
+    if (m == 8 || m == 16) return ref ? k_merge_check<16, true> : k_merge_check<16, false>;
+    if (m == 24) return ref ? k_merge_check<24, true> : k_merge_check<24, false>;
+    return ref ? k_merge_check<0, true> : k_merge_check<0, false>;
+}
+
 static int merge_check_launch(int n_active, int n, int cap, int n_up, int n_final, int max_bisect, int it, float eps,
                               float alpha_net, float beta_net, const float* dA, const float* sA, float* dB, float* sB,
                               const int* act, const float* d_new, const float* s_new, const float* u_final,
@@ -546,9 +591,11 @@ static int merge_check_launch(int n_active, int n, int cap, int n_up, int n_fina
                               int* act_out, int* act_count, float guard, int* esc_list, int* esc_count, void* stream) {
     if (n_active <= 0) return 0;
     SamplerParams P{n, cap, n_up, n_final, max_bisect, it, eps, alpha_net, beta_net, u_final_stride, guard, esc_list, esc_count};
-    const size_t lds = ((size_t)3 * n + 3 * n_up) * sizeof(float);
-    if (int rc = set_lds((const void*)k_merge_check, lds, kLdsRefusal)) return rc;
-    hipLaunchKernelGGL(k_merge_check, dim3(n_active), dim3(64), lds, (hipStream_t)stream, P, dA, sA, dB, sB, act, d_new,
+    const bool ref = perray_lds_ref();
+    const merge_check_fn kernel = merge_check_kernel(n + n_up, ref);
+    const size_t lds = (size_t)(ref ? 3 : 2) * ((size_t)n + n_up) * sizeof(float);
+    if (int rc = set_lds((const void*)kernel, lds, kLdsRefusal)) return rc;
+    hipLaunchKernelGGL(kernel, dim3(n_active), dim3(64), lds, (hipStream_t)stream, P, dA, sA, dB, sB, act, d_new,
                        s_new, u_final, d_fine, beta_plus, beta_map, iter_usage, act_out, act_count);
     NERFART_HIP(hipGetLastError());
     return 0;
@@ -718,7 +765,10 @@ static int fine_sample_run(const float* surf_blob, int precision, const float* e
     for (int it = 1; it <= max_iter && n_act > 0; ++it) {
         if (int rc = upsample_launch(n_act, n, cap, n_up, dA, sA, act, w.beta_plus, w.u_up, it > 1, w.d_new, stream)) return rc;
         if (int rc = nerfart_sdf_fwd_rays(surf_blob, precision, rays_o, rays_dn, act, w.d_new, n_act, n_up, n_up, R_bg, w.s_new, n_up, stream)) return rc;
-        if (int rc = merge_check_launch(n_act, n, cap, n_up, n_final, max_bisect, it, eps, alpha_net, beta_net, dA, sA,
+        // a guarded run escalates every ray still active after its last round (late_round, or max_iter): their beta+ is never read again (the
+        // second run starts from its own first check), so that round's rays skip the bisection
+        const bool last_round = guarded && (it == max_iter || (late_round > 0 && it >= late_round));
+        if (int rc = merge_check_launch(n_act, n, cap, n_up, n_final, last_round ? 0 : max_bisect, it, eps, alpha_net, beta_net, dA, sA,
                                         dB, sB, act, w.d_new, w.s_new, w.u_final, u_stride, d_fine, w.beta_plus,
                                         beta_map, iter_usage, act_next, w.count + it, guard, w.esc_list, w.count + ESC_SLOT, stream)) return rc;
         NERFART_HIP(hipMemcpyAsync(h_count, w.count, sizeof(h_count), hipMemcpyDeviceToHost, stream));
@@ -729,7 +779,7 @@ static int fine_sample_run(const float* surf_blob, int precision, const float* e
         t = sA; sA = sB; sB = t;
         int* ti = act; act = act_next; act_next = ti;
         n += n_up;
-        if (guarded && late_round > 0 && it >= late_round) break;       // the rays still active go to the escalation list below
+        if (last_round) break;                                          // the rays still active go to the escalation list below
     }
     if (!guarded) {
         if (n_act > 0)
@@ -811,14 +861,15 @@ typedef struct {
 } render_ws_t;
 
 // Buffers of the segment-ordered final stage (final_stage_skipping): the live lists of a ray group, alive flags, the live count, the per-ray running
-// optical depths, and the compact depth / sdf / nabla / radiance blocks of one segment launch.  They are carved out of the SAMPLER's region of the
-// render workspace: Algorithm 1 has finished by then and its rows (16 bytes x 512 (1 + rounds) per ray) are dead, so the workspace does not grow.
+// optical depths, the compact depth / sdf / nabla / radiance blocks of one segment launch and - own_h7 - that launch's h7 rows.  They are carved
+// out of the SAMPLER's region of the render workspace: Algorithm 1 has finished by then and its rows (16 bytes x 512 (1 + rounds) per ray) are
+// dead, so the workspace does not grow.
 typedef struct {
     int *live0, *live1, *alive, *n_live;
-    float *osum, *c_depth, *c_sdf, *c_nabla, *c_rad;
+    float *osum, *c_depth, *c_sdf, *c_nabla, *c_rad, *h7;
 } skip_ws_t;
 
-static skip_ws_t carve_skip(Carver& c, int R, int P, int G) {
+static skip_ws_t carve_skip(Carver& c, int R, int P, int G, bool own_h7) {
     skip_ws_t k;
     const size_t gpts = (size_t)G * (P < SKIP_SEG ? P : SKIP_SEG);
     k.live0 = c.take<int>((size_t)G);
@@ -830,21 +881,31 @@ static skip_ws_t carve_skip(Carver& c, int R, int P, int G) {
     k.c_sdf = c.take<float>(gpts);
     k.c_nabla = c.take<float>(gpts * 3);
     k.c_rad = c.take<float>(gpts * 3);
+    k.h7 = own_h7 ? c.take<float>(gpts * 256) : nullptr;
     return k;
 }
 
-// Rays per group: one segment launch of a full group has (about) as many points as one launch of the plain loop, G * min(SKIP_SEG, P) <=
-// min(k3_rays, R) * P, so the h7 carve holds it as it is (P = 192: G = 6 k3_rays) - halved until the buffers above fit the sampler's region
-// (they do at once for every reference configuration; with one ray per group they always do: the sampler holds several [R] arrays itself).
-static int skip_group_rays(int R, int P, int k3_rays, size_t room) {
+// Rays per group.  The groups exist only because a segment launch needs 1 KiB of h7 per point, and every launch of the two MLP kernels pays its own
+// fill, drain and tile quantisation, every segment of every group a host read: so ONE group of all R rays where the segment's h7 rows
+// (R min(SKIP_SEG, P) x 1 KiB; P = 192, 5 rounds: 33 KiB of the 48 KiB per ray) fit the sampler's dead region beside the buffers above (own_h7) -
+// halved while they do not.  Below G = min(k3_rays, R) P / min(SKIP_SEG, P) rays (P = 192: 6 k3_rays) the render workspace's own h7 carve holds
+// a segment launch as it is, and the group is halved only until the small buffers fit (with one ray per group they always do: the sampler holds
+// several [R] arrays itself).  The workspace's size is what it was.
+static int skip_group_rays(int R, int P, int k3_rays, size_t room, bool* own_h7) {
     const long long rk = k3_rays < R ? k3_rays : R;
-    long long g = rk * P / (P < SKIP_SEG ? P : SKIP_SEG);
-    if (g > R) g = R;
-    for (; g > 1; g /= 2) {
+    long long g_shared = rk * P / (P < SKIP_SEG ? P : SKIP_SEG);
+    if (g_shared > R) g_shared = R;
+    const auto fits = [&](long long g, bool own) {
         Carver c(nullptr);
-        carve_skip(c, R, P, (int)g);
-        if (c.off <= room) break;
-    }
+        carve_skip(c, R, P, (int)g, own);
+        return c.off <= room;
+    };
+    *own_h7 = true;
+    for (long long g = R; g > g_shared; g /= 2)
+        if (fits(g, true)) return (int)g;
+    *own_h7 = false;
+    long long g = g_shared;
+    for (; g > 1 && !fits(g, false); g /= 2) {}
     return (int)g;
 }
 
@@ -880,17 +941,20 @@ long long nerfart_volsdf_render_workspace_bytes(int n_rays, int n_samples, int n
 }
 
 // The final samples of every ray WITHOUT the ones behind full opacity (the rule and its derivation: next to SKIP_THETA).  Rays in groups
-// (skip_group_rays); per group the depth segments front to back: gather the live rays' depths of the segment, sdf + nabla and radiance on the live
-// list (slot-major compact outputs), scatter to [R, P], then advance the running optical depths, mark and zero-fill the dead, and compact the
-// list (stable: ascending ray order).  The live count reaches the host with ONE 4-byte read per segment per group (as the sampler's rounds do);
-// no live ray left ends the group; there are no zero-size launches.  Every stored value of an evaluated sample is what the plain loop stores.
+// (skip_group_rays: one group of all the rays where the workspace allows); per group the depth segments front to back: gather the live rays'
+// depths of the segment, sdf + nabla and radiance on the live list (slot-major compact outputs), then one launch scatters them to [R, P],
+// advances the running optical depths, marks and zero-fills the dead, and the list is compacted (stable: ascending ray order).  The live count
+// reaches the host with ONE 4-byte read per segment per group (as the sampler's rounds do); no live ray left ends the group; there are no
+// zero-size launches.  Every stored value of an evaluated sample is what the plain loop stores.
 static int final_stage_skipping(const render_ws_t& w, const float* surf_blob, int precision, const float* rad_blob, int rad_precision, int view_tiles,
                                 const float* rays_o, int n_rays, int P, float R_bg, float alpha, float beta, const float* d_all, float* sdf,
                                 float* nabla, float* rad, int k3_rays, hipStream_t stream) {
-    const int G = skip_group_rays(n_rays, P, k3_rays, w.sampler_bytes);
+    bool own_h7 = false;
+    const int G = skip_group_rays(n_rays, P, k3_rays, w.sampler_bytes, &own_h7);
     Carver carver(w.sampler);
-    const skip_ws_t k = carve_skip(carver, n_rays, P, G);
+    const skip_ws_t k = carve_skip(carver, n_rays, P, G, own_h7);
     if (carver.off > w.sampler_bytes) { set_last_error("render: workspace too small"); return 2; }
+    float* h7 = own_h7 ? k.h7 : w.h7;
     int *live = k.live0, *live_next = k.live1;
     for (int c0 = 0; c0 < n_rays; c0 += G) {
         int n_live = (n_rays - c0 < G) ? n_rays - c0 : G;
@@ -902,15 +966,14 @@ static int final_stage_skipping(const render_ws_t& w, const float* surf_blob, in
             hipLaunchKernelGGL(k_gather_segment_depths, dim3(nb), dim3(256), 0, stream, live, n_live, P, e0, len, d_all, k.c_depth);
             NERFART_HIP(hipGetLastError());
             if (int rc = nerfart_sdf_nabla_fwd_rays(surf_blob, precision, rays_o, w.rays_dn, live, k.c_depth, n_live, len, len, R_bg, k.c_sdf, k.c_nabla,
-                                                    w.h7, w.nabla_ws, (long long)w.nabla_ws_bytes, stream)) return rc;
+                                                    h7, w.nabla_ws, (long long)w.nabla_ws_bytes, stream)) return rc;
             if (int rc = nerfart_radiance_fwd_rays(rad_blob, rad_precision, view_tiles, rays_o, w.rays_dn, live, k.c_depth, n_live, len, len, k.c_nabla,
-                                                   w.h7, k.c_rad, stream)) return rc;
-            hipLaunchKernelGGL(k_scatter_segment, dim3(nb), dim3(256), 0, stream, live, n_live, P, e0, len, k.c_sdf, k.c_nabla, k.c_rad, sdf, nabla, rad);
+                                                   h7, k.c_rad, stream)) return rc;
+            const bool last = e0 + len >= P;                          // the last segment: nothing behind it to skip
+            hipLaunchKernelGGL(k_scatter_advance, dim3((n_live + 3) / 4), dim3(256), 0, stream, live, n_live, P, e0, len, last ? 0 : 1, k.c_sdf, k.c_nabla,
+                               k.c_rad, d_all, alpha, beta, k.osum, k.alive, sdf, nabla, rad);
             NERFART_HIP(hipGetLastError());
-            if (e0 + len >= P) break;                                 // the last segment: nothing behind it to skip
-            hipLaunchKernelGGL(k_advance_live, dim3((n_live + 3) / 4), dim3(256), 0, stream, live, n_live, P, e0, len, d_all, alpha, beta, k.osum,
-                               k.alive, sdf, nabla, rad);
-            NERFART_HIP(hipGetLastError());
+            if (last) break;
             hipLaunchKernelGGL(k_compact_live, dim3((n_live + 1023) / 1024), dim3(1024), 0, stream, live, k.alive, n_live, live_next, k.n_live);
             NERFART_HIP(hipGetLastError());
             NERFART_HIP(hipMemcpyAsync(&n_live, k.n_live, sizeof(int), hipMemcpyDeviceToHost, stream));
