@@ -543,6 +543,53 @@ int nerfart_mesh_compact_count(const int* label, const unsigned char* keep, cons
 int nerfart_mesh_compact_emit(const int* label, const unsigned char* keep, const int* faces, unsigned V, unsigned F, const void* ws, size_t ws_bytes,
                               int* src_vertex, int* faces_out, unsigned V_out, unsigned F_out, void* stream);
 
+/* ---- half-edge adjacency, manifold checks and per-component measures of an indexed mesh (csrc/mesh_topology.hip; mesh_util.half_edges /
+ * mesh_topology, tools/check_mesh.py: is the mesh a valid surface - watertight, how many holes, what genus).  Additions to ABI 5; no counterpart
+ * in the reference.  faces [F, 3] int32 over V vertices.  tests/mesh_topology_ref.py states all of this in numpy.  Everything but `measure` is
+ * integers: the results below are defined uniquely and do not depend on the table's size or on the order of work.
+ *   FACES: a face is BAD if an index lies outside [0, V); DEGENERATE if it is good but two of its indices are equal; otherwise PROPER.  Only
+ *     proper faces take part below; nothing is read or written outside the arrays because of the others.
+ *   HALF-EDGES: h = 3 f + i runs from faces[f][i] to faces[f][(i + 1) % 3]; it is also the CORNER of face f at vertex faces[f][i].
+ *   EDGES: for an undirected edge {a < b}, n_fwd and n_bwd count the proper half-edges a -> b and b -> a, n = n_fwd + n_bwd.  The edge is
+ *     BOUNDARY when n == 1; MANIFOLD when n_fwd == n_bwd == 1; FLIPPED when n == 2 otherwise (the two faces run through it the same way);
+ *     NON-MANIFOLD when n > 2.
+ *   FANS: across every edge with n == 2 (manifold or flipped) the two faces' corners at a are united, and likewise their corners at b.
+ *     vertex_fans[v] = the number of corner classes at v, 0 for a vertex in no proper face; more than one: a bow-tie.
+ *   BOUNDARY LOOPS: two boundary edges are joined when they share a vertex; loops are the classes of the closure, a loop's size its edges.
+ *   COMPONENTS are nerfart_mesh_components' labels; an edge or a face belongs to the component of its first vertex (a of {a < b}; faces[f][0]).
+ *   nerfart_mesh_topology_workspace_bytes: the caller's workspace for a table of 2^table_log2 slots, 1 <= table_log2 <= 31; table_log2 == 0
+ *     chooses the default, the smallest power of two >= 4 (3 F + 1) (at most 2^31): the distinct edges are at most 3 F, so the LOAD FACTOR
+ *     stays below 1/4, and is 1/16 .. 1/8 on a closed manifold mesh (E = 3 F / 2).  Carved in this order, each buffer rounded up to 256 bytes:
+ *     slot_of [3 F] u32, corner parents [3 F] u32, vertex parents [V] u32, loop sizes [V] u32, referenced [V] u32 (each of at least one word),
+ *     then the table, 24 bytes per slot {u64 key (a << 32) | b, u32 n_fwd, n_bwd, u32 smallest half-edge id fwd, bwd}.  Returns 0 (refused, see
+ *     nerfart_last_error) for V or F >= 2^31, 3 F >= 2^32, a table_log2 outside 0 .. 31 and a table of fewer than 3 F + 1 slots (so no table
+ *     at all once 3 F + 1 > 2^31: half-edge ids stay below 2^31 and never meet the codes of `twin`).
+ *   nerfart_mesh_half_edges: twin [3 F] int32 = the other half-edge of a manifold edge, -1 on a boundary edge, -2 on a flipped edge, -3 on a
+ *     non-manifold edge, -4 for the half-edges of a face that is not proper;  edge_uses [3 F] uint32 = n of the half-edge's edge, 0 for a face
+ *     that is not proper;  vertex_fans [V] uint32;  info [16] uint32 (DEVICE):
+ *       [0] proper faces  [1] degenerate faces  [2] bad faces  [3] referenced vertices (in a proper face)  [4] distinct edges E
+ *       [5] boundary edges  [6] flipped edges  [7] non-manifold edges  [8] vertices with more than one fan  [9] boundary loops
+ *       [10] edges of the longest loop  [11] OVERFLOW: 1 if a probe sequence visited every slot without finding room - it must read 0, and
+ *       does for every table this call accepts; with 1 the other outputs are not valid  [12 .. 15] zero.
+ *     Asynchronous, no host read inside.  Fills the workspace: it keeps the edge table for the call below.  F == 0 zeroes vertex_fans and
+ *     info; V == 0 counts every face as bad and writes -4 / 0.  Every loop is bounded whatever the faces hold: a probe sequence by the
+ *     table's size, the union-finds (csrc/union_find.h) by the indices.
+ *   nerfart_mesh_component_stats: from the SAME, untouched workspace and label [V] of nerfart_mesh_components:  counts [V, 6] uint32, indexed
+ *     BY LABEL, zero at every index that is not a label = {referenced vertices, edges, proper faces, boundary edges, flipped edges,
+ *     non-manifold edges};  measure [V, 2] fp64 (8-byte aligned) = {area, signed volume} summed over the component's proper faces.  verts
+ *     [V, 3] fp32 are promoted to fp64 first; then every operation is rounded once (no contraction), in this order, with a = v0, b = v1, c = v2:
+ *       u = b - a, w = c - a;  n = (uy wz - uz wy, uz wx - ux wz, ux wy - uy wx);  area term = 0.5 sqrt((nx nx + ny ny) + nz nz)
+ *       m = (by cz - bz cy, bz cx - bx cz, bx cy - by cx);  volume term = ((ax mx + ay my) + az mz) / 6
+ *     The terms are added with fp64 atomics (combined within a wave first): the order of the sum is not fixed, so a sum is within
+ *     m 2^-53 sum|term| of the exact sum of its m terms, and two runs can differ by that much.  The integer outputs are exact.
+ * Refused with 2 before any launch: a null pointer (of an array that is not empty), the sizes above, measure not 8-byte aligned, a workspace
+ * smaller than the query's answer (for nerfart_mesh_component_stats: than the answer for the smallest legal table) or not 16-byte aligned. */
+size_t nerfart_mesh_topology_workspace_bytes(unsigned V, unsigned F, int table_log2);
+int nerfart_mesh_half_edges(const int* faces, unsigned F, unsigned V, int table_log2, void* ws, size_t ws_bytes, int* twin, unsigned* edge_uses,
+                            unsigned* vertex_fans, unsigned* info, void* stream);
+int nerfart_mesh_component_stats(const float* verts, const int* faces, unsigned F, unsigned V, const int* label, const void* ws, size_t ws_bytes,
+                                 unsigned* counts, double* measure, void* stream);
+
 /* ---- mesh simplification by vertex clustering with quadric error metrics (csrc/mesh_simplify.hip; mesh_util.simplify_clusters,
  * extract_mesh(simplify_factor=); Lindstrom 2000, the representative placed as in dual contouring).  Additions to ABI 5; no counterpart in the
  * reference.  verts [V, 3] fp32 in GRID coordinates - grid point (i, j, k) sits at (i, j, k), nerfart_mc_emit with spacing 1, origin 0 -,

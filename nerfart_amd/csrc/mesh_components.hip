@@ -21,6 +21,7 @@
 //                  its scanned offset.  No atomics in the compaction: two runs give the same bits.  Every write is checked against V' / F'.
 // No workgroup waits for another, no kernel spins on a flag: every launch runs to completion on its own.
 #include "pair_scan.h"
+#include "union_find.h"
 #include <string>
 
 namespace nerfart {
@@ -42,37 +43,9 @@ static Workspace carve(void* base, size_t n) {
     return w;
 }
 
-// parent is read while other workgroups link under it: relaxed, agent scope - the value comes from the memory all of them write.
-__device__ __forceinline__ unsigned load_parent(const unsigned* parent, unsigned v) {
-    return __hip_atomic_load(parent + v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// The root of v's tree as this thread sees it.  BOUND: parent[x] <= x for every x at every moment - k_cc_init writes x, the only other writes are
-// the CAS of unite (lo < hi into parent[hi]) and k_cc_flatten's store of a root that find reached from x, hence <= x - so every step that does not
-// end the loop goes to a strictly smaller index: at most v steps.  A stale value is an older parent, still an ancestor and still <= x.
-__device__ __forceinline__ unsigned find(const unsigned* parent, unsigned v) {
-    for (;;) {
-        const unsigned p = load_parent(parent, v);
-        if (p >= v) return v;                      // p == v: a root (p > v cannot be; it would end the loop all the same)
-        v = p;
-    }
-}
-
-// Joins the trees of a and b.  The CAS links hi under lo only while hi is still a root, so a tree is never cut.  BOUND: when the CAS fails it
-// returns the parent another thread gave hi, old < hi (the invariant; it is not hi, or the CAS had succeeded); the retry goes on from (old, lo),
-// whose roots are <= old and <= lo, both < hi: max(hi, lo) strictly decreases on every retry - at most max(a, b) retries.
-__device__ __forceinline__ void unite(unsigned* parent, unsigned a, unsigned b) {
-    for (;;) {
-        a = find(parent, a);
-        b = find(parent, b);
-        if (a == b) return;
-        const unsigned hi = a > b ? a : b, lo = a > b ? b : a;
-        const unsigned old = atomicCAS(parent + hi, hi, lo);
-        if (old == hi) return;
-        a = old;
-        b = lo;
-    }
-}
+// the union-find (load_parent, find, unite and their bounds): csrc/union_find.h, shared with csrc/mesh_topology.hip
+using uf::find;
+using uf::unite;
 
 __global__ void __launch_bounds__(256) k_cc_init(unsigned* __restrict__ parent, unsigned* __restrict__ n_faces, unsigned V) {
     const unsigned v = blockIdx.x * 256u + threadIdx.x;

@@ -145,6 +145,9 @@ _SIGS = {
     "nerfart_mesh_compact_workspace_bytes": (_ll, [_i, _i]),
     "nerfart_mesh_compact_count": (_i, [_p, _p, _p, _i, _i, _p, _ll, _p, _p]),
     "nerfart_mesh_compact_emit": (_i, [_p, _p, _p, _i, _i, _p, _ll, _p, _p, _i, _i, _p]),
+    "nerfart_mesh_topology_workspace_bytes": (_ll, [_i, _i, _i]),
+    "nerfart_mesh_half_edges": (_i, [_p, _i, _i, _i, _p, _ll, _p, _p, _p, _p, _p]),
+    "nerfart_mesh_component_stats": (_i, [_p, _p, _i, _i, _p, _p, _ll, _p, _p, _p]),
     "nerfart_mesh_simplify_workspace_bytes": (_ll, [_i, _i, _i, _i, _i, _i]),
     "nerfart_mesh_simplify_count": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _ll, _p, _p, _p]),
     "nerfart_mesh_simplify_emit": (_i, [_p, _i, _i, _i, _i, _i, _i, _d, _p, _ll, _p, _p, _p, _i, _i, _p]),
@@ -489,6 +492,49 @@ def mesh_compact(label, keep, faces, V: int):
     ws, counts = mesh_compact_count(label, keep, faces, V)
     V_out, F_out = (int(c) for c in counts.cpu())
     return mesh_compact_emit(label, keep, faces, V, ws, V_out, F_out)
+
+
+def mesh_topology_workspace_bytes(V: int, F: int, table_log2: int = 0) -> int:
+    """nerfart_mesh_topology_workspace_bytes for an edge table of 2^table_log2 slots (0: the default, load factor below 1/4); bad sizes
+    (V or F >= 2^31, 3 F >= 2^32, a table of fewer than 3 F + 1 slots) raise with the library's message."""
+    n = int(lib.nerfart_mesh_topology_workspace_bytes(int(V), int(F), int(table_log2)))
+    _check(0 if n else 2, "nerfart_mesh_topology_workspace_bytes")
+    return n
+
+
+def mesh_half_edges(faces, V: int, table_log2: int = 0, ws=None):
+    """nerfart_mesh_half_edges on faces [F, 3] (int32) over V vertices: (ws, twin [3 F] int32, edge_uses [3 F] int32, vertex_fans [V] int32,
+    info [16] int32 - include/nerfart_hip.h names every index), all on faces' device.  ws is the filled workspace (uint8; a caller's own, or a
+    fresh one): it keeps the edge table and must stay untouched until mesh_component_stats has run.  No host synchronisation."""
+    V = int(V)
+    ptr, F = _mesh_faces(faces, V)
+    if ws is None:
+        ws = torch.empty(mesh_topology_workspace_bytes(V, F, table_log2), dtype=torch.uint8, device=faces.device)
+    twin = torch.empty(3 * F, dtype=torch.int32, device=faces.device)
+    uses = torch.empty(3 * F, dtype=torch.int32, device=faces.device)
+    fans = torch.empty(V, dtype=torch.int32, device=faces.device)
+    info = torch.empty(16, dtype=torch.int32, device=faces.device)
+    _check(lib.nerfart_mesh_half_edges(ptr, F, V, int(table_log2), _dev(ws, torch.uint8, "ws"), ws.numel(), twin.data_ptr(), uses.data_ptr(),
+                                       fans.data_ptr(), info.data_ptr(), _stream()), "nerfart_mesh_half_edges")
+    return ws, twin, uses, fans, info
+
+
+def mesh_component_stats(verts, faces, label, ws):
+    """nerfart_mesh_component_stats from the workspace mesh_half_edges filled for the same faces and the label [V] of mesh_components:
+    (counts [V, 6] int32 - by label: referenced vertices, edges, proper faces, boundary, flipped and non-manifold edges -, measure [V, 2]
+    float64 - by label: area, signed volume).  No host synchronisation."""
+    if verts.dim() != 2 or verts.shape[1] != 3:
+        raise NerfartHipError(f"verts must be [V, 3] (got {tuple(verts.shape)})")
+    V = int(verts.shape[0])
+    fp, F = _mesh_faces(faces, V)
+    if label.shape != (V,):
+        raise NerfartHipError(f"label must be [{V}] (got {tuple(label.shape)})")
+    counts = torch.empty(V, 6, dtype=torch.int32, device=faces.device)
+    measure = torch.empty(V, 2, dtype=torch.float64, device=faces.device)
+    _check(lib.nerfart_mesh_component_stats(_dev(verts, torch.float32, "verts"), fp, F, V, _dev(label, torch.int32, "label"),
+                                            _dev(ws, torch.uint8, "ws"), ws.numel(), counts.data_ptr(), measure.data_ptr(), _stream()),
+           "nerfart_mesh_component_stats")
+    return counts, measure
 
 
 def _mesh_simplify_args(verts, faces, dims, factor):

@@ -274,6 +274,84 @@ def filter_components(verts, faces, keep_largest=None, min_faces=None):
     return verts[src_vertex.long()], faces_out, src_vertex
 
 
+TOPOLOGY_INFO = ("proper_faces", "degenerate_faces", "bad_faces", "referenced_vertices", "edges", "boundary_edges", "flipped_edges",
+                 "nonmanifold_edges", "bowtie_vertices", "boundary_loops", "longest_loop", "overflow")      # info [0 .. 11] of nerfart_mesh_half_edges
+
+
+def _topology_faces(faces, who):
+    if not torch.is_tensor(faces) or not faces.is_cuda:
+        raise ValueError(f"{who}: faces must be a tensor on the GPU (there is no CPU path)")
+    if faces.dtype != torch.int32:
+        raise ValueError(f"{who}: faces must be {torch.int32} (got {faces.dtype})")
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"{who}: faces must be [n, 3] (got {tuple(faces.shape)})")
+    return faces.contiguous()
+
+
+def half_edges(faces, V: int, table_log2: int = 0):
+    """The half-edge adjacency of the indexed mesh faces [F, 3] (int32, on the GPU) over V vertices (csrc/mesh_topology.hip; the definitions are
+    in include/nerfart_hip.h): (twin [3 F] int32 - half-edge 3 f + i runs from faces[f][i] to faces[f][(i + 1) % 3]; the other half-edge of a
+    manifold edge, -1 on a boundary edge, -2 on a flipped edge (its two faces run through it the same way), -3 on an edge of more than two
+    faces, -4 for a face with an index outside [0, V) or with two equal indices -, edge_uses [3 F] int32 - the faces at the half-edge's edge -,
+    vertex_fans [V] int32 - the fans of faces around the vertex: 0 unreferenced, 1 regular, more: a bow-tie -, info [16] int32 - TOPOLOGY_INFO
+    names its counts), all on faces' device.  No host read.  table_log2 sizes the edge table (0: the default); the answers do not depend on it."""
+    from . import hip
+    faces = _topology_faces(faces, "half_edges")
+    if int(V) < 0:
+        raise ValueError(f"half_edges: V must be >= 0 (got {V})")
+    return hip.mesh_half_edges(faces, int(V), int(table_log2))[1:]
+
+
+def mesh_topology(verts, faces, components: bool = True):
+    """Is the mesh (verts [V, 3] float32, faces [F, 3] int32, on the GPU) a valid surface?  A dict of Python numbers and booleans after ONE host
+    read: the counts TOPOLOGY_INFO names (faces that are proper / degenerate / bad, referenced vertices, distinct edges, boundary / flipped /
+    non-manifold edges, vertices with more than one fan, boundary loops and the longest one's edges), euler = referenced vertices - edges + proper
+    faces, closed (no boundary edge), oriented (no flipped edge), manifold (no non-manifold edge, no bow-tie vertex) and watertight = closed and
+    oriented and manifold with no bad or degenerate face.  components=True adds "components": one dict per connected component (mesh_components'
+    labels and order: most faces first, ties to the smaller label; an unreferenced vertex is a component without faces) with label, vertices,
+    edges, faces, boundary_edges, flipped_edges, nonmanifold_edges, bowtie_vertices, euler, closed, area, volume (signed; fp64 sums over the
+    component's faces) and genus = (2 - euler) / 2 - only where the component is closed, oriented and manifold, otherwise None; and "tensors":
+    label [V] int32, counts [V, 6] int32 and measure [V, 2] float64, both indexed by label, on the device.  Nothing is repaired."""
+    from . import hip
+    verts, faces = _distance_mesh(verts, faces, "mesh_topology")
+    V = int(verts.shape[0])
+    ws, twin, uses, fans, info = hip.mesh_half_edges(faces, V)
+    if not components:
+        got = info.cpu().tolist()
+    else:
+        label, n_faces, _ = hip.mesh_components(faces, V)
+        counts, measure = hip.mesh_component_stats(verts, faces, label, ws)
+        bow = torch.zeros(V, dtype=torch.int32, device=faces.device).index_add_(0, label.long(), (fans > 1).to(torch.int32))
+        packed = torch.cat([info, label, bow, n_faces, counts.reshape(-1), measure.reshape(-1).view(torch.int32)]).cpu().numpy()      # the one host read
+        got = packed[:16].tolist()
+    out = {k: int(x) for k, x in zip(TOPOLOGY_INFO, got)}
+    # the flag is known only after the one host read: the stats above have then run on a table that is not valid, which is harmless (every index
+    # they take from the workspace is checked against the arrays) - nothing of it is returned
+    if out["overflow"]:
+        raise RuntimeError("mesh_topology: the edge table overflowed (nerfart_mesh_half_edges info[11]); the counts are not valid")
+    out["euler"] = out["referenced_vertices"] - out["edges"] + out["proper_faces"]
+    out["closed"] = out["boundary_edges"] == 0
+    out["oriented"] = out["flipped_edges"] == 0
+    out["manifold"] = out["nonmanifold_edges"] == 0 and out["bowtie_vertices"] == 0
+    out["watertight"] = out["closed"] and out["oriented"] and out["manifold"] and out["bad_faces"] == 0 and out["degenerate_faces"] == 0
+    if components:
+        lab, bw, nf = packed[16:16 + V], packed[16 + V:16 + 2 * V], packed[16 + 2 * V:16 + 3 * V]
+        cnt = packed[16 + 3 * V:16 + 9 * V].reshape(V, 6)
+        msr = packed[16 + 9 * V:].copy().view(np.float64).reshape(V, 2)
+        roots = np.nonzero(lab == np.arange(V, dtype=np.int32))[0]
+        roots = roots[np.argsort(-nf[roots].astype(np.int64), kind="stable")]      # mesh_components' ranking: stable over ascending labels
+        out["components"] = []
+        for r in roots.tolist():
+            v, e, f, b, fl, nm = (int(x) for x in cnt[r])
+            euler = v - e + f
+            ok = b == 0 and fl == 0 and nm == 0 and bw[r] == 0
+            out["components"].append({"label": r, "vertices": v, "edges": e, "faces": f, "boundary_edges": b, "flipped_edges": fl,
+                                      "nonmanifold_edges": nm, "bowtie_vertices": int(bw[r]), "euler": euler, "closed": b == 0,
+                                      "area": float(msr[r, 0]), "volume": float(msr[r, 1]), "genus": (2 - euler) // 2 if ok else None})
+        out["tensors"] = {"label": label, "counts": counts, "measure": measure}
+    return out
+
+
 def simplify_clusters(verts_grid, faces, shape, factor, reg: float = 0.01):
     """Vertex clustering with quadric error metrics (csrc/mesh_simplify.hip; the rules are in include/nerfart_hip.h): the vertices verts_grid [V, 3]
     (float32, on the GPU, in GRID coordinates of a grid of shape = (nx, ny, nz): grid point (i, j, k) sits at (i, j, k)) are merged per block of

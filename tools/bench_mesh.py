@@ -16,7 +16,10 @@ figures have been taken.  `--distance [--distance_samples S]` (with --simplify) 
 against marching cubes' own, in grid cells: the stages each alone - sampling (nerfart_mesh_sample_count, _emit), the grid build of the undecimated
 mesh (nerfart_mesh_grid_count + _fill, with its host read) and the query (nerfart_mesh_closest) of S samples of the simplified mesh -,
 mesh_util.mesh_distance as a whole (both directions), and the distances it found; with --narrow_band also the distance between the banded
-sweep's mesh and the dense one."""
+sweep's mesh and the dense one.  `--topology` adds the half-edge adjacency and manifold report (csrc/mesh_topology.hip) of the
+extracted mesh, and of the simplified one with --simplify: nerfart_mesh_half_edges and nerfart_mesh_component_stats each alone, beside
+nerfart_mesh_components on the same mesh (the yardstick for "a pass over the faces"), the edge table's size, mesh_util.mesh_topology as a whole
+(with its one host read) and the dict it returns (components cut to the five largest)."""
 import argparse, json, os, statistics, sys, tempfile, time
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -49,6 +52,7 @@ def main():
     ap.add_argument("--render", type=int, nargs=2, default=None, metavar=("H", "W"), help="also time the rasteriser on the extracted mesh at this image size")
     ap.add_argument("--distance", action="store_true", help="also time mesh_util.mesh_distance of the simplified mesh against the extracted one (needs --simplify)")
     ap.add_argument("--distance_samples", type=int, default=1 << 20)
+    ap.add_argument("--topology", action="store_true", help="also time mesh_util.half_edges / component_stats and report the topology of the mesh(es)")
     args = ap.parse_args()
     if args.distance and not args.simplify:
         ap.error("--distance compares the simplified mesh with the extracted one: give --simplify C")
@@ -97,6 +101,28 @@ def main():
                                            args.iters)
         res.update(simplify_factor=c, simplified_vertices=int(out_v.shape[0]), simplified_triangles=int(out_f.shape[0]),
                    simplify_workspace_MiB=round(sws.numel() / 2 ** 20, 1))
+    if args.topology:                                              # adjacency and manifold report, in grid coordinates
+        def topology(tag, tv, tf):
+            Vt, Ft = int(tv.shape[0]), int(tf.shape[0])
+            tws = torch.empty(hip.mesh_topology_workspace_bytes(Vt, Ft), dtype=torch.uint8, device=dev)
+            hip.mesh_half_edges(tf, Vt, ws=tws)                    # warm-ups
+            label, _, _ = hip.mesh_components(tf, Vt)
+            hip.mesh_component_stats(tv, tf, label, tws)
+            res[tag + "half_edges_ms"], _ = timed(lambda: hip.mesh_half_edges(tf, Vt, ws=tws), args.iters)
+            res[tag + "component_stats_ms"], _ = timed(lambda: hip.mesh_component_stats(tv, tf, label, tws), args.iters)
+            res[tag + "mesh_components_ms"], _ = timed(lambda: hip.mesh_components(tf, Vt), args.iters)
+            res[tag + "mesh_topology_ms"], report = timed(lambda: mesh_util.mesh_topology(tv, tf), max(3, args.iters // 4))
+            del report["tensors"]
+            report["n_components"], report["components"] = len(report["components"]), report["components"][:5]
+            # the default table's size, asked of the library: the table_log2 whose workspace is the default's (at these sizes every table is a
+            # multiple of 256 bytes, so exactly one matches)
+            slots = 1 << [k for k in range(1, 32) if int(hip.lib.nerfart_mesh_topology_workspace_bytes(Vt, Ft, k)) == tws.numel()][-1]
+            res.update({tag + "topology": report, tag + "topology_workspace_MiB": round(tws.numel() / 2 ** 20, 1), tag + "topology_table_slots": slots,
+                        tag + "topology_table_MiB": round(slots * 24 / 2 ** 20, 1), tag + "topology_table_load": round(report["edges"] / slots, 4),
+                        tag + "topology_probe_length": "not measured"})
+        topology("", *hip.mc_emit(vol, 0.0, [0.0] * 3, [1.0] * 3, ws, V, F))
+        if args.simplify:
+            topology("simplified_", out_v, out_f)
     if args.distance:                                              # the simplified mesh against the extracted one, in grid cells
         S, seed = args.distance_samples, 0
         grid = mesh_util.default_distance_grid(F)
