@@ -590,6 +590,77 @@ int nerfart_mesh_half_edges(const int* faces, unsigned F, unsigned V, int table_
 int nerfart_mesh_component_stats(const float* verts, const int* faces, unsigned F, unsigned V, const int* label, const void* ws, size_t ws_bytes,
                                  unsigned* counts, double* measure, void* stream);
 
+/* ---- manifold repair: cut and stitch of non-manifold edges (csrc/mesh_repair.hip; mesh_util.repair_manifold, extract_mesh(repair=)).  Additions
+ * to ABI 5; no counterpart in the reference.  verts [V, 3] fp32, faces [F, 3] int32.  The output has no non-manifold edge and no bow-tie
+ * vertex; no triangle's geometry changes, except that a few triangles are split at an edge midpoint where an indexed mesh forces it (rule 5).
+ * tests/mesh_repair_ref.py states all of this in numpy.  Everything but the midpoints is integers and the midpoints are two correctly rounded
+ * fp32 operations: every output is defined uniquely and depends neither on the order of work nor on the table's size.  Faces, half-edges,
+ * corners and edges are those of the topology block above.
+ *   0. FACES: bad and degenerate faces are dropped.
+ *   1. CANCEL: the proper faces are grouped by vertex set {a, b, c}.  Of a set with p faces of one orientation and q of the other, |p - q| faces
+ *      of the majority orientation survive, the first in input order; the rest are dropped - zero-thickness fins (a, b, c) + (a, c, b) go in
+ *      pairs, each pair taking one forward and one backward use from each of the three edges, so an edge's balance is kept.  (Faces of ONE
+ *      orientation only all survive: dropping a duplicate would break the balance.  Their edges are flipped edges, see below.)  The groups are
+ *      found with an open-addressing table of face indices keyed on the sorted triple (atomicCAS from empty, atomicMin among equal keys, as the
+ *      duplicate table of the simplify block); a slot's counts are sums and its members a set: the outcome does not depend on the order of work.
+ *      Only the surviving faces take part below.
+ *   2. RADIAL PAIRING of every non-manifold edge {a < b} with 2 < n <= 64 half-edges.  Its half-edges are ordered around the axis
+ *      d = v_b - v_a by the direction of their APEX, the face's third vertex.  Vertices are promoted to fp64; then every operation is rounded
+ *      once (no contraction), in this order; no division, square root or atan2:
+ *        sub(p, q) = (px - qx, py - qy, pz - qz);  cross(p, q) = (py qz - pz qy, pz qx - px qz, px qy - py qx);  dot(p, q) = (px qx + py qy) + pz qz
+ *        d = sub(v_b, v_a);  w = sub(apex, v_a);  w0 = the w of the edge's smallest half-edge id;  u1 = cross(d, w0);  u2 = cross(d, u1)
+ *        (x, y) = (-dot(w, u2), dot(w, u1)); the half-edge with the smallest id is given (1, 0) exactly.  (Scaling y by a positive constant
+ *        keeps the cyclic order: nothing is normalised.)
+ *      i COMES BEFORE j: by half-plane first - "y < 0, or y == 0 and x < 0" is the second -; within a half-plane when
+ *      c = x_i y_j - x_j y_i > 0, not when c < 0; any other outcome (c == 0, a NaN) is a TIE, which goes to the smaller half-edge id - so
+ *      degenerate and non-finite geometry orders by id alone.  A half-edge's position is the NUMBER of half-edges of its edge that come before
+ *      it, equal numbers in ascending id: defined whatever rounding does to the transitivity of the comparison, and independent of any sorting
+ *      algorithm.  The order starts at the smallest id.  A backward half-edge b -> a has the solid just after it in this order, a forward one
+ *      just before it.  wedge 0 = VOID: forward half-edges open, backward ones close - a pair bounds an empty wedge, solids touching along the
+ *      edge become one solid.  wedge 1 = SOLID: backward opens, forward closes - the solids are separated.  Bracket matching over the cyclic
+ *      sequence: an opener is pushed (first turn only), a closer pops the last opener and the two are a PAIR; two turns around the cycle.
+ *      Unmatched half-edges stay UNPAIRED (an unbalanced edge) and end as boundary edges.  An edge with n > 64 is WIDE: left entirely unpaired.
+ *   3. CORNER CLASSES: across every edge with n == 2 (manifold, or flipped: a flipped edge is LEFT AS IT IS, orientation repair is out of
+ *      scope) and across every pair, the two faces' corners at a are united, and their corners at b.  Every class is one output vertex; the
+ *      classes are numbered ascending by (original vertex, smallest corner id of the class): V1 of them.  Unreferenced vertices vanish.
+ *   4. MULTI-EDGES: the UNITS of an edge with 2 < n <= 64 are its pairs and its unpaired half-edges.  Two units can land on the same (class at
+ *      a, class at b) - the umbrellas at both ends are connected through other faces -, which an indexed mesh cannot express.  Of the units
+ *      with one class pair, the one holding the smallest half-edge id keeps the edge; every other unit is SUBDIVIDED.
+ *   5. SUBDIVISION: a subdivided unit gets one new vertex m = (v_a + v_b) * 0.5f - fp32, the add, then the multiply.  The M new vertices follow
+ *      the V1 class vertices, ordered by the unit's smallest half-edge id.  A face with k = 1 .. 3 subdivided half-edges becomes k + 1 faces:
+ *      its polygon is its corners in order with the midpoint of half-edge i inserted after corner i, rotated to start at the midpoint of the
+ *      face's lowest subdivided half-edge, and fanned from there: (P0, Pj, Pj+1), j = 1 .. k + 1 - no triangle of that fan is collinear.  The
+ *      first triangle takes the face's place, the others are appended after all surviving faces in (face, fan) order.
+ *   6. OUTPUT: verts_out [V1 + M, 3]; src_vertex [V1 + M] int32 = the original vertex of a class, -1 for a midpoint; mid_ends [M, 2] int32 =
+ *      the output indices of a midpoint's edge ends (at a, at b), for interpolating per-vertex attributes; faces_out = the surviving faces in
+ *      input order with the new indices (not rotated), then the appended ones.  Positions come from scans (csrc/pair_scan.h): no atomic
+ *      decides one.
+ *   GUARANTEE: with wide == 0 and overflow == 0, nerfart_mesh_half_edges of the output reports no non-manifold edge, no bow-tie vertex, no
+ *      degenerate and no bad face; if moreover unpaired == 0 and the surviving faces had no boundary and no flipped edge, the output is
+ *      watertight.  Repairing the output again returns it unchanged.
+ *   nerfart_mesh_repair_workspace_bytes: as nerfart_mesh_topology_workspace_bytes (the same table, the same table_log2 rule, the same
+ *     refusals); about 80 bytes per half-edge beside the table.
+ *   nerfart_mesh_repair_count: fills the workspace, counts [4] (DEVICE, 8-byte aligned) = {V1, M, surviving faces, appended faces} and info [16]
+ *     uint32 (DEVICE): [0] bad faces dropped  [1] degenerate faces dropped  [2] faces cancelled  [3] non-manifold edges met  [4] of them,
+ *     edges in which at least one pair was made  [5] half-edges left unpaired (those of wide edges included)  [6] wide edges
+ *     [7] vertices split: V1 minus the vertices referenced by a surviving face  [8] units subdivided = M  [9] ties met in the angular
+ *     comparisons, one per unordered pair of half-edges  [10] OVERFLOW of a table: must read 0, and does for every table this call accepts
+ *     [11 .. 15] zero.  Asynchronous, no host read inside.  Every loop is bounded whatever the faces hold: probe sequences by the tables'
+ *     sizes, the walk of a cancel group by its size (only a face of a group with both orientations and p != q walks), the per-edge loops by
+ *     64, the ranking of a vertex's classes by their number, the union-finds by the indices.
+ *   nerfart_mesh_repair_emit: from the SAME, untouched workspace, the same mesh and table_log2: the four output arrays.  V_out = V1 + M rows
+ *     of verts_out and src_vertex, M_out rows of mid_ends, F_out rows of faces_out are the sizes of the caller's arrays (every write is
+ *     checked against them).
+ * Refused with 2 before any launch: a null pointer (of an array that is not empty), V or F >= 2^31, 3 F >= 2^32, a table_log2 outside 0 .. 31
+ * or a table of fewer than 3 F + 1 slots, wedge not 0 or 1, counts not 8-byte aligned, M_out > V_out, V_out > 6 F, F_out > 4 F, a workspace
+ * smaller than the query's answer (or not 16-byte aligned). */
+size_t nerfart_mesh_repair_workspace_bytes(unsigned V, unsigned F, int table_log2);
+int nerfart_mesh_repair_count(const float* verts, const int* faces, unsigned V, unsigned F, int wedge, int table_log2, void* ws, size_t ws_bytes,
+                              unsigned* counts, unsigned* info, void* stream);
+int nerfart_mesh_repair_emit(const float* verts, const int* faces, unsigned V, unsigned F, int table_log2, const void* ws, size_t ws_bytes,
+                             float* verts_out, int* faces_out, int* src_vertex, int* mid_ends, unsigned V_out, unsigned M_out, unsigned F_out,
+                             void* stream);
+
 /* ---- mesh simplification by vertex clustering with quadric error metrics (csrc/mesh_simplify.hip; mesh_util.simplify_clusters,
  * extract_mesh(simplify_factor=); Lindstrom 2000, the representative placed as in dual contouring).  Additions to ABI 5; no counterpart in the
  * reference.  verts [V, 3] fp32 in GRID coordinates - grid point (i, j, k) sits at (i, j, k), nerfart_mc_emit with spacing 1, origin 0 -,

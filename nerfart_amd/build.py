@@ -16,8 +16,8 @@ import sys
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libnerfart_hip.so")
 PUBLIC_HEADER = os.path.join(os.path.dirname(os.path.dirname(CSRC)), "include", "nerfart_hip.h")     # the C ABI: every source is compiled against it
-SOURCES = ["capi_common.cpp", "wgrad.hip", "pass2_operands.hip", "render_backward.hip", "mlp_chain.hip", "mlp_chain_bf16.hip", "mlp_chain_f16x2.hip", "mlp_chain_f16x1.hip", "mlp_k2_f16x1_to.hip", "mlp_k2_w32.hip", "mlp_grad_bf16.hip", "mlp_backward_bf16.hip", "volsdf_render.hip", "volsdf_backward.hip", "volsdf_geo_backward.hip", "neus_render.hip", "raygen.hip", "clip_vit.hip", "style_heads.hip", "ray_casting.hip", "vgg_conv.hip", "pack_blob.hip", "geo_feature.hip", "marching_cubes.hip", "mesh_vertices.hip", "mesh_components.hip", "mesh_topology.hip", "mesh_band.hip", "mesh_simplify.hip", "mesh_texture.hip", "mesh_raster.hip", "mesh_distance.hip"]
-HEADERS = ["nerfart_common.h", "host_util.h", "ray_common.h", "sample_cdf.h", "mlp_common.h", "mlp_bf16_core.h", "gemm_f16.h", "gemm_f32.h", "mc_table.h", "pair_scan.h", "union_find.h"]
+SOURCES = ["capi_common.cpp", "wgrad.hip", "pass2_operands.hip", "render_backward.hip", "mlp_chain.hip", "mlp_chain_bf16.hip", "mlp_chain_f16x2.hip", "mlp_chain_f16x1.hip", "mlp_k2_f16x1_to.hip", "mlp_k2_w32.hip", "mlp_grad_bf16.hip", "mlp_backward_bf16.hip", "volsdf_render.hip", "volsdf_backward.hip", "volsdf_geo_backward.hip", "neus_render.hip", "raygen.hip", "clip_vit.hip", "style_heads.hip", "ray_casting.hip", "vgg_conv.hip", "pack_blob.hip", "geo_feature.hip", "marching_cubes.hip", "mesh_vertices.hip", "mesh_components.hip", "mesh_topology.hip", "mesh_repair.hip", "mesh_band.hip", "mesh_simplify.hip", "mesh_texture.hip", "mesh_raster.hip", "mesh_distance.hip"]
+HEADERS = ["nerfart_common.h", "host_util.h", "ray_common.h", "sample_cdf.h", "mlp_common.h", "mlp_bf16_core.h", "gemm_f16.h", "gemm_f32.h", "mc_table.h", "pair_scan.h", "union_find.h", "edge_table.h"]
 INCLUDES = {"mlp_chain_f16x2.hip": ["mlp_chain_bf16.hip", "mlp_grad_bf16.hip"], "mlp_chain_f16x1.hip": ["mlp_chain_bf16.hip"]}      # sources compiled a second time (precision 4)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize", "-x", "hip"]
 # TEST-ONLY variant libraries (never loaded by the product: nerfart_amd.hip binds libnerfart_hip.so): the same objects with ONE source compiled with

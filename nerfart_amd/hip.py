@@ -148,6 +148,9 @@ _SIGS = {
     "nerfart_mesh_topology_workspace_bytes": (_ll, [_i, _i, _i]),
     "nerfart_mesh_half_edges": (_i, [_p, _i, _i, _i, _p, _ll, _p, _p, _p, _p, _p]),
     "nerfart_mesh_component_stats": (_i, [_p, _p, _i, _i, _p, _p, _ll, _p, _p, _p]),
+    "nerfart_mesh_repair_workspace_bytes": (_ll, [_i, _i, _i]),
+    "nerfart_mesh_repair_count": (_i, [_p, _p, _i, _i, _i, _i, _p, _ll, _p, _p, _p]),
+    "nerfart_mesh_repair_emit": (_i, [_p, _p, _i, _i, _i, _p, _ll, _p, _p, _p, _p, _i, _i, _i, _p]),
     "nerfart_mesh_simplify_workspace_bytes": (_ll, [_i, _i, _i, _i, _i, _i]),
     "nerfart_mesh_simplify_count": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _ll, _p, _p, _p]),
     "nerfart_mesh_simplify_emit": (_i, [_p, _i, _i, _i, _i, _i, _i, _d, _p, _ll, _p, _p, _p, _i, _i, _p]),
@@ -535,6 +538,55 @@ def mesh_component_stats(verts, faces, label, ws):
                                             _dev(ws, torch.uint8, "ws"), ws.numel(), counts.data_ptr(), measure.data_ptr(), _stream()),
            "nerfart_mesh_component_stats")
     return counts, measure
+
+
+MESH_REPAIR_WEDGES = ("void", "solid")      # nerfart_mesh_repair_count's wedge = the index
+
+
+def mesh_repair_workspace_bytes(V: int, F: int, table_log2: int = 0) -> int:
+    """nerfart_mesh_repair_workspace_bytes for an edge table of 2^table_log2 slots (0: the default); bad sizes (V or F >= 2^31, 3 F >= 2^32, a
+    table of fewer than 3 F + 1 slots) raise with the library's message."""
+    n = int(lib.nerfart_mesh_repair_workspace_bytes(int(V), int(F), int(table_log2)))
+    _check(0 if n else 2, "nerfart_mesh_repair_workspace_bytes")
+    return n
+
+
+def _mesh_repair_args(verts, faces):
+    if verts.dim() != 2 or verts.shape[1] != 3:
+        raise NerfartHipError(f"verts must be [V, 3] (got {tuple(verts.shape)})")
+    V = int(verts.shape[0])
+    fp, F = _mesh_faces(faces, V)
+    return _dev(verts, torch.float32, "verts"), fp, V, F
+
+
+def mesh_repair_count(verts, faces, wedge: str = "void", table_log2: int = 0, ws=None):
+    """nerfart_mesh_repair_count on verts [V, 3] float32 and faces [F, 3] int32: (ws, counts, info) - the filled workspace (uint8; a caller's
+    own, or a fresh one: it must stay untouched until mesh_repair_emit has run), the int32 device tensors counts [4] = (class vertices V1,
+    midpoints M, surviving faces, appended faces) and info [16] (include/nerfart_hip.h names every index).  No host synchronisation."""
+    if wedge not in MESH_REPAIR_WEDGES:
+        raise NerfartHipError(f"wedge must be one of {MESH_REPAIR_WEDGES} (got {wedge!r})")
+    vp, fp, V, F = _mesh_repair_args(verts, faces)
+    if ws is None:
+        ws = torch.empty(mesh_repair_workspace_bytes(V, F, table_log2), dtype=torch.uint8, device=faces.device)
+    counts = torch.empty(4, dtype=torch.int32, device=faces.device)
+    info = torch.empty(16, dtype=torch.int32, device=faces.device)
+    _check(lib.nerfart_mesh_repair_count(vp, fp, V, F, MESH_REPAIR_WEDGES.index(wedge), int(table_log2), _dev(ws, torch.uint8, "ws"), ws.numel(),
+                                         counts.data_ptr(), info.data_ptr(), _stream()), "nerfart_mesh_repair_count")
+    return ws, counts, info
+
+
+def mesh_repair_emit(verts, faces, ws, V1: int, M: int, F_out: int, table_log2: int = 0):
+    """nerfart_mesh_repair_emit from the workspace mesh_repair_count filled for the same mesh (and the same table_log2): (verts' [V1 + M, 3]
+    float32, faces' [F_out, 3] int32, src_vertex [V1 + M] int32, mid_ends [M, 2] int32)."""
+    vp, fp, V, F = _mesh_repair_args(verts, faces)
+    V_out = int(V1) + int(M)
+    out_v = torch.empty(V_out, 3, dtype=torch.float32, device=faces.device)
+    out_f = torch.empty(int(F_out), 3, dtype=torch.int32, device=faces.device)
+    src = torch.empty(V_out, dtype=torch.int32, device=faces.device)
+    ends = torch.empty(int(M), 2, dtype=torch.int32, device=faces.device)
+    _check(lib.nerfart_mesh_repair_emit(vp, fp, V, F, int(table_log2), _dev(ws, torch.uint8, "ws"), ws.numel(), out_v.data_ptr(), out_f.data_ptr(),
+                                        src.data_ptr(), ends.data_ptr(), V_out, int(M), int(F_out), _stream()), "nerfart_mesh_repair_emit")
+    return out_v, out_f, src, ends
 
 
 def _mesh_simplify_args(verts, faces, dims, factor):

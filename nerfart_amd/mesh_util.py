@@ -30,7 +30,9 @@ and colours every texel at its own point, `texel_points` says where that is (csr
 integer coverage, a depth test by integer atomics, per-pixel face / barycentrics / depth / normal, then per-vertex colours or the baked texture.
 `read_ply` / `read_obj` read back the files `write_ply` / `write_obj` write.  `sample_surface` / `closest_on_mesh` / `mesh_distance` say how far one
 mesh is from another - Chamfer, Hausdorff, F-score - from area-weighted samples and exact closest-point queries (csrc/mesh_distance.hip;
-tools/compare_mesh.py).  None of it is on the render or train path.
+tools/compare_mesh.py).  `half_edges` / `mesh_topology` say whether a mesh is a valid surface (csrc/mesh_topology.hip; tools/check_mesh.py), and
+`repair_manifold` - extract_mesh(repair=True) - makes it one: non-manifold edges and bow-tie vertices are cut and stitched (csrc/mesh_repair.hip).
+None of it is on the render or train path.
 """
 import types
 
@@ -311,7 +313,7 @@ def mesh_topology(verts, faces, components: bool = True):
     labels and order: most faces first, ties to the smaller label; an unreferenced vertex is a component without faces) with label, vertices,
     edges, faces, boundary_edges, flipped_edges, nonmanifold_edges, bowtie_vertices, euler, closed, area, volume (signed; fp64 sums over the
     component's faces) and genus = (2 - euler) / 2 - only where the component is closed, oriented and manifold, otherwise None; and "tensors":
-    label [V] int32, counts [V, 6] int32 and measure [V, 2] float64, both indexed by label, on the device.  Nothing is repaired."""
+    label [V] int32, counts [V, 6] int32 and measure [V, 2] float64, both indexed by label, on the device.  Nothing is repaired here: repair_manifold does that."""
     from . import hip
     verts, faces = _distance_mesh(verts, faces, "mesh_topology")
     V = int(verts.shape[0])
@@ -350,6 +352,36 @@ def mesh_topology(verts, faces, components: bool = True):
                                       "area": float(msr[r, 0]), "volume": float(msr[r, 1]), "genus": (2 - euler) // 2 if ok else None})
         out["tensors"] = {"label": label, "counts": counts, "measure": measure}
     return out
+
+
+REPAIR_INFO = ("dropped_bad", "dropped_degenerate", "dropped_cancelled", "nonmanifold_edges", "edges_paired", "unpaired_half_edges", "wide_edges",
+               "vertices_split", "pairs_subdivided", "sort_ties", "overflow")      # info [0 .. 10] of nerfart_mesh_repair_count
+REPAIR_WEDGES = ("void", "solid")
+
+
+def repair_manifold(verts, faces, wedge: str = "void", table_log2: int = 0):
+    """Cut and stitch the non-manifold edges of the mesh (verts [V, 3] float32, faces [F, 3] int32, on the GPU; csrc/mesh_repair.hip, the rules are
+    in include/nerfart_hip.h): bad, degenerate and mutually cancelling faces are dropped, the faces around every edge of more than two are paired
+    in angular order - wedge="void": the pairs bound the empty wedges, so solids that touch along an edge become one; wedge="solid": they are
+    separated -, every vertex is split into one copy per fan of faces, and where two pairs of one edge would still share both ends one of them
+    is split at the edge's midpoint.  No other triangle changes.  Returns (verts' [V', 3], faces' [F', 3], src_vertex [V'] int32 - the original
+    vertex of every new one, -1 for a midpoint -, mid_ends [M, 2] int32 - the new indices of a midpoint's edge ends, the midpoints being the last
+    M vertices: any per-vertex attribute is attr[src_vertex] with the mean of attr'[mid_ends] at the midpoints -, info: a dict of the counts
+    REPAIR_INFO names).  With info["wide_edges"] == 0 the output has no non-manifold edge and no bow-tie vertex; with no unpaired half-edge, and
+    neither boundary nor flipped edges in the input, it is watertight.  Flipped edges are left as they are.  Small closed pieces that splitting
+    sets free are the caller's to drop (filter_components).  Everything stays on the GPU; ONE host read (the sizes and info) between counting
+    and emitting; two calls give identical tensors, whatever table_log2 (the edge table's size; 0: the default)."""
+    from . import hip
+    if wedge not in REPAIR_WEDGES:
+        raise ValueError(f"repair_manifold: wedge must be one of {REPAIR_WEDGES} (got {wedge!r})")
+    verts, faces = _distance_mesh(verts, faces, "repair_manifold")
+    ws, counts, info = hip.mesh_repair_count(verts, faces, wedge, int(table_log2))
+    got = torch.cat([counts, info]).cpu().tolist()                              # the one host read
+    V1, M, Fa, Fx = got[:4]
+    report = {k: int(x) for k, x in zip(REPAIR_INFO, got[4:])}
+    if report["overflow"]:
+        raise RuntimeError("repair_manifold: a table overflowed (nerfart_mesh_repair_count info[10]); nothing was emitted")
+    return hip.mesh_repair_emit(verts, faces, ws, V1, M, Fa + Fx, int(table_log2)) + (report,)
 
 
 def simplify_clusters(verts_grid, faces, shape, factor, reg: float = 0.01):
@@ -868,6 +900,10 @@ def _check_extract_options(o):
         raise ValueError(f"extract_mesh: backend must be 'native' or 'skimage' (got {o.backend!r})")
     if int(o.refine_evals) < 0:
         raise ValueError(f"extract_mesh: refine_evals must be >= 0 (got {int(o.refine_evals)})")
+    if o.repair_wedge not in REPAIR_WEDGES:
+        raise ValueError(f"extract_mesh: repair_wedge must be one of {REPAIR_WEDGES} (got {o.repair_wedge!r})")
+    if o.repair and o.backend != "native":
+        raise ValueError("extract_mesh: repair needs backend='native' (the mesh is repaired on the GPU)")
 
 
 def _extract_skimage(implicit_surface, volume_size, level, N, filepath, chunk, reference_shear):
@@ -909,6 +945,26 @@ def _normals_and_colors(implicit_surface, color_model, pts):
     return hip.normalize_dirs(implicit_surface.forward_with_nablas(pts)[1].contiguous()), None
 
 
+def _repaired_rows(rows, src_vertex, mid_ends):
+    """A per-vertex array [V, k] carried through repair_manifold: rows[src_vertex], and at the midpoints - the last M rows, src_vertex -1 -
+    the mean of the two ends' rows."""
+    M = int(mid_ends.shape[0])
+    out = rows[src_vertex.clamp(min=0).long()]
+    if M:
+        out[out.shape[0] - M:] = (out[mid_ends[:, 0].long()] + out[mid_ends[:, 1].long()]) * 0.5
+    return out
+
+
+def _repair_stage(mesh, o):
+    """Stage 4b on a mesh no vertex of which has been queried yet: repair_manifold in the placement frame; the vertices in any other frame are
+    the old ones' copies, the midpoints the means of their ends there."""
+    verts, faces, src, ends, info = repair_manifold(mesh.verts, mesh.faces, o.repair_wedge)
+    if o.repair_info is not None:
+        o.repair_info.update(info)
+    old = mesh
+    return _Mesh(verts, faces, None if old.place is None else (lambda origin, spacing: _repaired_rows(old.points(origin, spacing), src, ends)))
+
+
 @torch.no_grad()
 def _extract_native(implicit_surface, o):
     """extract_mesh(backend="native") after validation, o its arguments: the stages of extract_mesh's docstring, in its order."""
@@ -931,10 +987,18 @@ def _extract_native(implicit_surface, o):
         if filtering:                                               # before clustering can weld a floater to the surface
             grid, faces, _ = filter_components(grid, faces, o.keep_largest, o.min_component_faces)
         grid, faces, _ = simplify_clusters(grid, faces, vol.shape, o.simplify_factor, o.simplify_reg)
+        if o.repair:                                                # on grid coordinates: the midpoints are vertices like the others
+            grid, faces, _, _, info = repair_manifold(grid, faces, o.repair_wedge)
+            if o.repair_info is not None:
+                o.repair_info.update(info)
         mesh = _Mesh(grid_to_frame(grid, *placement), faces, lambda origin, spacing: grid_to_frame(grid, origin, spacing))
+    elif o.repair:                                                  # stage 6 first, then the repair, both before any vertex is queried
+        if filtering:
+            mesh.verts, mesh.faces, mesh.src = filter_components(mesh.verts, mesh.faces, o.keep_largest, o.min_component_faces)
+        mesh = _repair_stage(mesh, o)
     if o.vertex_normals or o.color_model is not None:
         mesh.normals, mesh.colors = _normals_and_colors(implicit_surface, o.color_model, mesh.points(*model))
-    if filtering and o.simplify_factor is None:
+    if filtering and o.simplify_factor is None and not o.repair:
         mesh.verts, mesh.faces, mesh.src = filter_components(mesh.verts, mesh.faces, o.keep_largest, o.min_component_faces)
         mesh.normals, mesh.colors = (a if a is None else a[mesh.src.long()] for a in (mesh.normals, mesh.colors))
     normals = mesh.normals if o.vertex_normals else None
@@ -950,7 +1014,8 @@ def extract_mesh(implicit_surface, volume_size=2.0, level=0.0, N=512, filepath="
                  reference_shear: bool = False, backend: str = "native", refine_evals: int = 0, vertex_normals: bool = False, color_model=None,
                  keep_largest: int = None, min_component_faces: int = None, narrow_band: bool = False, band_brick: int = 8,
                  band_lipschitz: float = BAND_LIPSCHITZ, band_info: dict = None, simplify_factor: int = None, simplify_reg: float = 0.01,
-                 texture_model=None, texture_patch: int = 4, texture_project: int = 0):
+                 texture_model=None, texture_patch: int = 4, texture_project: int = 0, repair: bool = False, repair_wedge: str = "void",
+                 repair_info: dict = None):
     """mesh_util.extract_mesh: SDF volume -> marching cubes -> a mesh file; returns filepath.  At the defaults: the reference's call and its
     two-element PLY.  Two frames: the mesh is PLACED as the reference places it, spacing volume_size / N, offset -volume_size / 2 (mesh_util.py:112;
     placement_frame); every network query of a vertex or texel is made in the MODEL's frame, the swept grid's, spacing volume_size / (N - 1)
@@ -971,6 +1036,12 @@ def extract_mesh(implicit_surface, volume_size=2.0, level=0.0, N=512, filepath="
       4. simplify_factor=c >= 2, on grid coordinates: keep_largest / min_component_faces drop the floaters first - clustering could weld them to
          the surface -, then the vertices of every block of c^3 grid cells become one, placed by the quadrics of the block's faces
          (simplify_clusters; csrc/mesh_simplify.hip; simplify_reg pulls it toward the members' mean): roughly c^2 times fewer triangles.
+         repair=True (off by default: every file stays the same byte for byte) then makes the mesh a 2-manifold: repair_manifold
+         (csrc/mesh_repair.hip) cuts and stitches the non-manifold edges and bow-tie vertices clustering leaves - simplify_clusters keeps a
+         surface closed and oriented, not manifold -, repair_wedge="void" (solids touching along an edge become one) or "solid" (they are
+         separated); a dict passed as repair_info receives its counts.  Without simplify_factor the repair runs after stage 6's filter, which
+         then comes before stage 5.  Small closed pieces the splitting sets free stay: keep_largest / min_component_faces run BEFORE the repair;
+         filter_components on the written mesh is the caller's tool for them.  Flipped edges are left as they are.
       5. At the vertices there are now: vertex_normals writes nx ny nz = the normalised SDF gradient, color_model (the whole VolSDF / NeuS model)
          red green blue = its radiance looking down the normal (vertex_attributes).
       6. Without simplify_factor, keep_largest / min_component_faces (the sheared grid included): only the keep_largest largest connected components,
@@ -985,7 +1056,8 @@ def extract_mesh(implicit_surface, volume_size=2.0, level=0.0, N=512, filepath="
     reference_shear, with backend="skimage", with texture_patch < 1 or texture_project < 0; simplify_factor, then narrow_band, with reference_shear
     (clusters and bricks are blocks of the regular lattice) or backend="skimage" (the clustering runs on the native extractor's vertices; Lewiner's
     ambiguity tests would read fill values); keep_largest / min_component_faces off the native backend (the components are found on the GPU);
-    stage 3 with reference_shear or off the native backend (no regular frame; no edge table); an unknown backend; refine_evals < 0."""
+    stage 3 with reference_shear or off the native backend (no regular frame; no edge table); an unknown backend; refine_evals < 0; a
+    repair_wedge that is neither "void" nor "solid"; repair off the native backend."""
     o = types.SimpleNamespace(**locals())                            # the arguments as one value: the checks and the stages read them by name
     o.edges = bool(refine_evals or vertex_normals or color_model is not None or simplify_factor is not None or texture_model is not None)   # stage 3
     _check_extract_options(o)

@@ -19,7 +19,10 @@ mesh_util.mesh_distance as a whole (both directions), and the distances it found
 sweep's mesh and the dense one.  `--topology` adds the half-edge adjacency and manifold report (csrc/mesh_topology.hip) of the
 extracted mesh, and of the simplified one with --simplify: nerfart_mesh_half_edges and nerfart_mesh_component_stats each alone, beside
 nerfart_mesh_components on the same mesh (the yardstick for "a pass over the faces"), the edge table's size, mesh_util.mesh_topology as a whole
-(with its one host read) and the dict it returns (components cut to the five largest)."""
+(with its one host read) and the dict it returns (components cut to the five largest).  `--repair [--repair_wedge W]` adds the manifold repair
+(csrc/mesh_repair.hip) of the extracted mesh, and of the simplified one with --simplify: mesh_util.repair_manifold as a whole (with its one host
+read), nerfart_mesh_repair_count and _emit each alone, nerfart_mesh_half_edges on the same mesh in the same run (the yardstick: the pass
+contains one half-edge build), the workspace, the counts it reports, and mesh_util.mesh_topology of the repaired mesh."""
 import argparse, json, os, statistics, sys, tempfile, time
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -53,6 +56,8 @@ def main():
     ap.add_argument("--distance", action="store_true", help="also time mesh_util.mesh_distance of the simplified mesh against the extracted one (needs --simplify)")
     ap.add_argument("--distance_samples", type=int, default=1 << 20)
     ap.add_argument("--topology", action="store_true", help="also time mesh_util.half_edges / component_stats and report the topology of the mesh(es)")
+    ap.add_argument("--repair", action="store_true", help="also time mesh_util.repair_manifold on the mesh(es) and report the repaired topology")
+    ap.add_argument("--repair_wedge", default="void", choices=["void", "solid"])
     args = ap.parse_args()
     if args.distance and not args.simplify:
         ap.error("--distance compares the simplified mesh with the extracted one: give --simplify C")
@@ -123,6 +128,28 @@ def main():
         topology("", *hip.mc_emit(vol, 0.0, [0.0] * 3, [1.0] * 3, ws, V, F))
         if args.simplify:
             topology("simplified_", out_v, out_f)
+    if args.repair:                                                # cut and stitch, in grid coordinates
+        def repair(tag, tv, tf):
+            Vt, Ft, wedge = int(tv.shape[0]), int(tf.shape[0]), args.repair_wedge
+            rws = torch.empty(hip.mesh_repair_workspace_bytes(Vt, Ft), dtype=torch.uint8, device=dev)
+            tws = torch.empty(hip.mesh_topology_workspace_bytes(Vt, Ft), dtype=torch.uint8, device=dev)
+            _, counts, _ = hip.mesh_repair_count(tv, tf, wedge, ws=rws)     # warm-ups; the sizes
+            V1, M, Fa, Fx = (int(c) for c in counts.cpu())
+            hip.mesh_repair_emit(tv, tf, rws, V1, M, Fa + Fx)
+            hip.mesh_half_edges(tf, Vt, ws=tws)
+            res[tag + "repair_manifold_ms"], out = timed(lambda: mesh_util.repair_manifold(tv, tf, wedge), args.iters)
+            res[tag + "repair_count_ms"], _ = timed(lambda: hip.mesh_repair_count(tv, tf, wedge, ws=rws), args.iters)
+            res[tag + "repair_emit_ms"], _ = timed(lambda: hip.mesh_repair_emit(tv, tf, rws, V1, M, Fa + Fx), args.iters)
+            res[tag + "repair_half_edges_ms"], _ = timed(lambda: hip.mesh_half_edges(tf, Vt, ws=tws), args.iters)
+            report = mesh_util.mesh_topology(out[0], out[1])
+            del report["tensors"]
+            report["n_components"], report["components"] = len(report["components"]), report["components"][:5]
+            res.update({tag + "repair_wedge": wedge, tag + "repair_info": out[4], tag + "repair_workspace_MiB": round(rws.numel() / 2 ** 20, 1),
+                        tag + "repaired_vertices": int(out[0].shape[0]), tag + "repaired_triangles": int(out[1].shape[0]),
+                        tag + "repaired_topology": report})
+        repair("", *hip.mc_emit(vol, 0.0, [0.0] * 3, [1.0] * 3, ws, V, F))
+        if args.simplify:
+            repair("simplified_", out_v, out_f)
     if args.distance:                                              # the simplified mesh against the extracted one, in grid cells
         S, seed = args.distance_samples, 0
         grid = mesh_util.default_distance_grid(F)

@@ -8,7 +8,10 @@ genus, how large - for a file extract_mesh wrote, before it goes to a printer, a
 of proper / degenerate / bad faces, referenced vertices, edges, boundary / flipped / non-manifold edges, vertices with more than one fan,
 boundary loops and the longest one; euler; closed, oriented, manifold, watertight - with the component list (most faces first: label, vertices,
 edges, faces, boundary_edges, euler, closed, area, volume, genus, ...) cut to `--components K` entries (default 10; n_components says how many
-there are), and the file under "mesh".  Nothing is repaired.
+there are), and the file under "mesh".  Nothing is repaired unless `--repair` is given.
+`--repair OUT.ply [--repair_wedge void|solid]` writes the mesh after mesh_util.repair_manifold (csrc/mesh_repair.hip: non-manifold edges and bow-tie
+vertices cut and stitched; positions and faces only, no per-vertex attribute is carried over) and prints a SECOND JSON line: {"repair": its
+counts, "repaired": the same report of the repaired mesh}.
 `--defects OUT.ply` writes the mesh with per-vertex colours; the first rule that applies decides:
     red      the vertices of boundary edges (edges in one face);
     magenta  the vertices of non-manifold edges (in more than two faces) and of flipped edges (their two faces run through them the same way);
@@ -32,6 +35,8 @@ def parse(argv=None):
     ap.add_argument("--mesh", type=str, required=True, help="the mesh (.ply or .obj)")
     ap.add_argument("--components", type=int, default=10, help="how many components to list, largest first")
     ap.add_argument("--defects", type=str, default=None, help="write the mesh with per-vertex colours marking its defects (.ply)")
+    ap.add_argument("--repair", type=str, default=None, help="write the mesh after repair_manifold (.ply) and print its report as a second line")
+    ap.add_argument("--repair_wedge", type=str, default="void", choices=["void", "solid"], help="the pairing rule of --repair")
     return ap.parse_args(argv)
 
 
@@ -63,9 +68,21 @@ def defect_colors(faces, V):
     return colors
 
 
+def report(verts, faces, components):
+    """mesh_topology's dict without its tensors, the component list cut to `components` entries"""
+    from nerfart_amd import mesh_util
+    out = mesh_util.mesh_topology(verts, faces)
+    del out["tensors"]
+    out["n_components"] = len(out["components"])
+    out["components"] = out["components"][:components]
+    return out
+
+
 def main(argv=None):
     from nerfart_amd import mesh_util
     args = parse(argv)
+    if args.repair is not None and not args.repair.endswith(".ply"):
+        raise ValueError(f"--repair writes a PLY: the path must end in .ply (got {args.repair!r})")
     if args.defects is not None and not args.defects.endswith(".ply"):
         raise ValueError(f"--defects writes a PLY: the path must end in .ply (got {args.defects!r})")
     if args.components < 0:
@@ -73,15 +90,18 @@ def main(argv=None):
     assert torch.cuda.is_available(), "check_mesh needs the GPU (nerfart_amd has no CPU path)"
     dev = torch.device("cuda", 0)
     verts, faces = load_mesh(args.mesh, dev)
-    out = mesh_util.mesh_topology(verts, faces)
-    del out["tensors"]
-    out["n_components"] = len(out["components"])
-    out["components"] = out["components"][:args.components]
+    out = report(verts, faces, args.components)
     out["mesh"] = {"path": args.mesh, "vertices": int(verts.shape[0]), "faces": int(faces.shape[0])}
     if args.defects is not None:
         mesh_util.write_ply(args.defects, verts, faces, colors=defect_colors(faces, int(verts.shape[0])).cpu().numpy())
         out["defects"] = args.defects
     print(json.dumps(out))
+    if args.repair is not None:
+        rverts, rfaces, _, _, info = mesh_util.repair_manifold(verts, faces, args.repair_wedge)
+        mesh_util.write_ply(args.repair, rverts, rfaces)
+        fixed = report(rverts, rfaces, args.components)
+        fixed["mesh"] = {"path": args.repair, "vertices": int(rverts.shape[0]), "faces": int(rfaces.shape[0])}
+        print(json.dumps({"repair": dict(info, wedge=args.repair_wedge), "repaired": fixed}))
 
 
 if __name__ == "__main__":

@@ -12,7 +12,10 @@ decimates the mesh on the GPU before it is written: the vertices of every block 
 the block's faces (mesh_util.simplify_clusters), after the floaters are gone and before normals and colours are queried.  `--texture
 [--texture_patch P --texture_project K]` with `--out mesh.obj` writes a textured mesh instead of a PLY - mesh.obj, mesh.mtl, mesh.png: every face
 of the final mesh gets a patch of P texel intervals along its legs in a per-face atlas, baked on the GPU from the radiance net looking down the
-normal (mesh_util.bake_texture); K Newton steps put the texels of a decimated face back onto the surface first.  Without --load_pt the mesh is the model's sphere initialisation.  `--k1:k2 v` overrides of the config work as everywhere (nerfart_amd.config)."""
+normal (mesh_util.bake_texture); K Newton steps put the texels of a decimated face back onto the surface first.  `--repair [--repair_wedge
+void|solid]` makes the mesh a 2-manifold before it is written (mesh_util.repair_manifold: the non-manifold edges and bow-tie vertices --simplify
+leaves are cut and stitched; solids touching along an edge become one with `void`, are separated with `solid`) and prints its counts as one JSON
+line.  Without --load_pt the mesh is the model's sphere initialisation.  `--k1:k2 v` overrides of the config work as everywhere (nerfart_amd.config)."""
 import json
 import os
 import sys
@@ -55,6 +58,10 @@ def parse(argv=None):
     parser.add_argument("--texture_patch", type=int, default=4, help="texel intervals along a triangle's legs in the atlas of --texture (>= 1)")
     parser.add_argument("--texture_project", type=int, default=0, help="Newton steps that move the texels of --texture onto the level set before "
                                                                        "they are coloured (2 is plenty after --simplify)")
+    parser.add_argument("--repair", action="store_true", help="cut and stitch non-manifold edges and bow-tie vertices (what --simplify leaves) before "
+                                                              "normals, colours and texture are queried; prints the repair's counts")
+    parser.add_argument("--repair_wedge", type=str, default="void", choices=["void", "solid"], help="how --repair pairs the faces around an edge of "
+                        "more than two: 'void' joins solids that touch along it, 'solid' separates them")
     args, unknown = parser.parse_known_args(argv)
     return args, cfg.load_config(args, unknown)
 
@@ -69,15 +76,17 @@ def main():
         state = torch.load(args.load_pt, map_location="cpu")
         model.load_state_dict(state["model"] if "model" in state else state)
     model.to(dev)
-    info = {}
+    info, repair_info = {}, {}
     path = mesh_util.extract_mesh(model.implicit_surface, volume_size=args.volume_size, level=args.level, N=args.N, filepath=args.out, chunk=args.chunk,
                                   refine_evals=args.refine, vertex_normals=args.normals, color_model=model if args.colors else None,
                                   keep_largest=args.keep_largest, min_component_faces=args.min_faces, narrow_band=args.narrow_band,
                                   band_brick=args.band_brick, band_lipschitz=args.band_lipschitz, band_info=info, simplify_factor=args.simplify,
                                   simplify_reg=args.simplify_reg, texture_model=model if args.texture else None, texture_patch=args.texture_patch,
-                                  texture_project=args.texture_project)
+                                  texture_project=args.texture_project, repair=args.repair, repair_wedge=args.repair_wedge, repair_info=repair_info)
     if args.narrow_band:
         print(json.dumps(info))
+    if args.repair:
+        print(json.dumps(repair_info))
     print(path)
 
 
